@@ -2,10 +2,15 @@
 """Headline benchmark: jacobi2d float 16384 x 16384, iterate 1000 (BASELINE.json
 configs[3], the configuration the metric is quoted on; it fits one MI355X).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one whole 1000-iteration sweep of the grid, input already resident
-in HBM.  N > 1 is launched by torch.distributed.run, one rank per GPU: the grid
+in HBM.  A plain run sets up, warms up (plus the tuning step that picks the split of
+`iterate` on this device), times the K steps and prints the line; `--full` adds what
+takes runs of its own: the per-launch `roofline` entry and the shader clock probe,
+BASELINE configs 2, 3 and 5 (N = 1, headline workload) and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs below).
+N > 1 is launched by torch.distributed.run, one rank per GPU: the grid
 is cut into N slabs along the outer dimension (strong scaling: the grid is fixed)
 and neighbours exchange ghost rows over RCCL every E iterations; E and the order of
 exchange and sweeps (serial, or overlapped on a side stream) are the fastest of a few
@@ -14,15 +19,15 @@ candidates timed during warm-up (`config.exchange_candidates_ms`), unless `--exc
 
 Prints ONE JSON line (rank 0).  `value` = valid cell-updates / wall time, valid =
 the cells the reference semantics define (the box shrinks by the stencil radius
-every iteration).  `roofline` describes the dominant kernel
-(roofline_block below): `bound` names its binding physical limit - HBM traffic
+every iteration).  `roofline` (--full) describes the dominant
+kernel (roofline_block below): `bound` names its binding physical limit - HBM traffic
 (PMC bytes of this kernel on this grid, from profiles/rNN_traffic.json) or VALU
 issue (useful f32 lane-operations against the chip's 78.6 T/s) - and `frac` the
 fraction of that limit's peak; `frac_algorithmic` is SURVEY 8(d)'s figure
 (algorithmic bytes per update / time / 8 TB/s), which temporal blocking pushes
-past 1 and which is therefore not a bound.  `cpu_baseline` is the CPU oracle (a
-port of the loop nest the reference emits into `<app>_test`) timed on this host's
-cores on a bounded sample.
+past 1 and which is therefore not a bound.  `cpu_baseline` (--full) is the CPU
+oracle (a port of the loop nest the reference emits into `<app>_test`) timed on this
+host's cores on a bounded sample.
 """
 import argparse
 import json
@@ -38,6 +43,8 @@ for p in (ROOT, os.path.join(ROOT, 'soda-compiler_amd')):
 import numpy as np  # noqa: E402
 
 SEED = 20240607
+# --dump-outputs: at most this many bytes in all; a larger output is sampled
+DUMP_BYTES = 32 << 20
 HBM_PEAK_GBPS = 8000.0   # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
 
 
@@ -55,12 +62,20 @@ def parse_args():
   ap.add_argument('--exchange', type=int, default=0,
                   help='N > 1: iterations between halo exchanges (0 = the fastest of '
                        '1, 2, 4, 8 x the deepest fused kernel, timed during warm-up)')
+  ap.add_argument('--full', action='store_true',
+                  help='besides the headline figure: the roofline entry and shader clock '
+                       'probe, the other BASELINE configs and the CPU baseline (a plain run '
+                       'does only what the headline figure needs)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                  help='N = 1: write the output arrays of the last timed step as '
+                       'DIR/<output>.npy (float32 / float64; a seeded sample of the cells '
+                       'beyond %d MiB in all)' % (DUMP_BYTES >> 20))
   ap.add_argument('--cpu-seconds', type=float, default=12.0,
-                  help='CPU baseline sample budget (0 = skip)')
+                  help='--full: CPU baseline sample budget (0 = skip)')
   ap.add_argument('--cpu-baseline-at-all-n', action='store_true',
-                  help='N > 1: rank 0 times the CPU baseline as well (by default it is on '
-                       'the N = 1 line only: it is a property of the host, and 12 s of every '
-                       'multi-GPU run would go into it)')
+                  help='--full, N > 1: rank 0 times the CPU baseline as well (by default it '
+                       'is on the N = 1 line only: it is a property of the host, and 12 s of '
+                       'every multi-GPU run would go into it)')
   ap.add_argument('--force-dist', action='store_true',
                   help='take the torch.distributed slab path even with 1 rank')
   ap.add_argument('--overlap', action='store_true',
@@ -90,12 +105,15 @@ def parse_args():
                        'passes repeat the schedule of the timed run with it); implies '
                        '--no-tune (soda_hip_plan_set_split)')
   ap.add_argument('--no-other-configs', action='store_true',
-                  help='N = 1, headline workload: do not time BASELINE configs 2, 3 and 5 '
-                       'after it (config.other_configs)')
+                  help='--full, N = 1, headline workload: do not time BASELINE configs 2, 3 '
+                       'and 5 after it (config.other_configs)')
   ap.add_argument('--jit', action='store_true',
                   help='compile the kernels with hiprtc instead of loading the '
                        'code object built by __graft_entry__.build()')
-  return ap.parse_args()
+  args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error('--steps must be at least 1 and --warmup at least 0')
+  return args
 
 
 def open_program(app, iterate, jit):
@@ -411,11 +429,43 @@ OTHER_CONFIGS = (
 OTHER_STEPS, OTHER_WARMUP = 30, 10
 
 
+def dump_outputs(folder, spec, program, dout, dims, iterate):
+  """--dump-outputs: the output arrays as a caller of the sweep receives them (cells
+  outside an output's own box are zero, Program.run_numpy) as DIR/<output>.npy, in
+  float32 (float32 and up-to-16-bit outputs, exactly) or float64.  An output larger than
+  its share of DUMP_BYTES is written as a seeded sample instead: the values at the sorted
+  distinct C-order flat indices np.unique(default_rng(SEED).integers(0, cells, n)), n =
+  the share / element size - the same cells for the same shape on every run."""
+  from soda_hip.codegen import spec as specmod
+  os.makedirs(folder, exist_ok=True)
+  shape = tuple(reversed(dims))
+  cells = int(np.prod(shape))
+  boxes = specmod.iteration_boxes(spec, iterate)[-1]
+  for name, d, dt in zip(spec['outputs'], dout, program.out_dtypes):
+    wide = np.dtype(np.float32 if dt == np.float32 or dt.itemsize <= 2 else np.float64)
+    a = d.download(shape, dt)
+    lo, hi = boxes[name]
+    box = [(-lo[k], max(-lo[k], dims[k] - hi[k])) for k in reversed(range(spec['dim']))]
+    n = DUMP_BYTES // len(spec['outputs']) // wide.itemsize
+    if cells <= n:
+      out = np.zeros(shape, wide)
+      sl = tuple(slice(b0, b1) for b0, b1 in box)
+      out[sl] = a[sl]
+    else:
+      idx = np.unique(np.random.default_rng(SEED).integers(0, cells, size=n))
+      inside = np.ones(idx.shape, bool)
+      for c, (b0, b1) in zip(np.unravel_index(idx, shape), box):
+        inside &= (c >= b0) & (c < b1)
+      out = np.where(inside, a.reshape(-1)[idx], 0).astype(wide)
+    np.save(os.path.join(folder, name + '.npy'), out)
+
+
 def measure(app, dims, iterate, steps, warmup, max_depth=0, split='', no_tune=False,
-            jit=False):
+            jit=False, full=False, dump=''):
   """One workload under the bench protocol on the current device: `warmup` untimed
-  sweeps (+ the tuning step), `steps` timed ones, then the same sweep under per-launch
-  events for the roofline entry.  Returns (result line, spec)."""
+  sweeps (+ the tuning step), `steps` timed ones; `dump` = a folder for the outputs of
+  the last timed sweep; `full`: then the same sweep under per-launch events and the clock
+  probe for the roofline entry.  Returns (result line, spec)."""
   import torch
   from soda_hip.codegen import spec as specmod
   from soda_hip.runtime import host
@@ -451,21 +501,9 @@ def measure(app, dims, iterate, steps, warmup, max_depth=0, split='', no_tune=Fa
     program.sweep(ip, op, dims, iterate)
   sync()
   wall = time.perf_counter() - t0
-  # the same loop under hipEvents, per launch, for the roofline entry: three repeats,
-  # every launch at its fastest
-  timing = program.sweep_timed(ip, op, dims, iterate, warmup=0, repeats=3)
+  if dump:
+    dump_outputs(dump, spec, program, dout, dims, iterate)
   schedule = program.schedule(dims, iterate)
-  # the shader clock under this load, measured in-run: a probe wavefront sleeps beside
-  # ~30 ms of the same sweeps and counts shader cycles against the constant 100 MHz clock
-  # (not in the profiling passes, which repeat a given split: their kernel counts stay
-  # sweeps x launches per sweep)
-  clock = None
-  if not split:
-    probe_sweeps = max(1, int(0.03 / max(wall / steps, 1e-6)))
-    clock = program.shader_clock_during(
-        lambda: [program.sweep(ip, op, dims, iterate) for _ in range(probe_sweeps)],
-        probe_sweeps * wall / steps)
-    sync()
   valid = specmod.valid_cells(spec, dims, iterate)
   nominal = cells * iterate
   ms_per_step = wall / steps * 1e3
@@ -483,7 +521,7 @@ def measure(app, dims, iterate, steps, warmup, max_depth=0, split='', no_tune=Fa
           iterate), app=app, dims=dims, iterate=iterate,
                   valid_cell_updates=valid, nominal_cell_updates=nominal,
                   nominal_gcell_updates_per_s=nominal / (wall / steps) / 1e9,
-                  launches_per_step=timing['launches'],
+                  launches_per_step=len(schedule),
                   depth_schedule=schedule_text(schedule),
                   depth_split='given (--split)' if split else
                   'measured (soda_hip_plan_tune)' if not no_tune and
@@ -495,11 +533,26 @@ def measure(app, dims, iterate, steps, warmup, max_depth=0, split='', no_tune=Fa
                   'measured (%d kernel x box)' % program.tuned_streams()
                   if program.tuned_streams() else 'calibrated (confirmed by measurement)',
                   effective_GBps=valid * abytes / (wall / steps) / 1e9,
-                  device=host.device_info(0)['arch']),
-      roofline=roofline_block(spec, program, schedule,
-                              per_iteration_updates(spec, dims, iterate),
-                              timing, dims, iterate, step_us=ms_per_step * 1e3,
-                              clock=clock))
+                  device=host.device_info(0)['arch']))
+  if full:
+    # the same loop under hipEvents, per launch, for the roofline entry: three repeats,
+    # every launch at its fastest
+    timing = program.sweep_timed(ip, op, dims, iterate, warmup=0, repeats=3)
+    # the shader clock under this load, measured in-run: a probe wavefront sleeps beside
+    # ~30 ms of the same sweeps and counts shader cycles against the constant 100 MHz
+    # clock (not in the profiling passes, which repeat a given split: their kernel counts
+    # stay sweeps x launches per sweep)
+    clock = None
+    if not split:
+      probe_sweeps = max(1, int(0.03 / max(wall / steps, 1e-6)))
+      clock = program.shader_clock_during(
+          lambda: [program.sweep(ip, op, dims, iterate) for _ in range(probe_sweeps)],
+          probe_sweeps * wall / steps)
+      sync()
+    result['roofline'] = roofline_block(spec, program, schedule,
+                                        per_iteration_updates(spec, dims, iterate),
+                                        timing, dims, iterate, step_us=ms_per_step * 1e3,
+                                        clock=clock)
   for d in din + dout:
     d.free()
   program.close()
@@ -545,12 +598,16 @@ def is_headline(args):
 def run_single(args):
   result, spec = measure(args.app, args.size, args.iterate, args.steps, args.warmup,
                          max_depth=args.max_depth, split=args.split,
-                         no_tune=args.no_tune, jit=args.jit)
+                         no_tune=args.no_tune, jit=args.jit, full=args.full,
+                         dump=args.dump_outputs)
+  if not args.full:
+    return result
   if is_headline(args) and not args.no_other_configs and not args.split:
     others = []
     for tag, app, dims, iterate in OTHER_CONFIGS:
       try:
-        line, _ = measure(app, dims, iterate, OTHER_STEPS, OTHER_WARMUP, jit=args.jit)
+        line, _ = measure(app, dims, iterate, OTHER_STEPS, OTHER_WARMUP, jit=args.jit,
+                          full=True)
         others.append(other_config_entry(tag, line))
       except Exception as e:   # noqa: BLE001 - a secondary config must not cost the headline
         others.append(dict(config=tag, error='%s: %s' % (type(e).__name__, str(e)[:300])))
@@ -566,6 +623,8 @@ def main():
   # image already; kept for environments built by hand)
   os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
   world = int(os.environ.get('WORLD_SIZE', '1'))
+  if args.dump_outputs and (args.gpus > 1 or world > 1 or args.force_dist):
+    raise SystemExit('--dump-outputs: single-GPU runs only (N = 1, no --force-dist)')
   if args.gpus > 1 and 'RANK' not in os.environ:
     # started by hand without a launcher: start one rank per GPU as CHILD
     # processes (nothing here has touched the GPU yet) and pass their status on
@@ -582,7 +641,8 @@ def main():
   if args.gpus > 1 or world > 1 or args.force_dist:
     from soda_hip.runtime import dist
     result = dist.bench_main(args, open_program, make_input, per_iteration_updates,
-                             roofline_block, schedule_text, cpu_baseline)
+                             roofline_block, schedule_text,
+                             cpu_baseline if args.full else None)
   else:
     result = run_single(args)
   if result is not None:

@@ -1636,7 +1636,7 @@ def test_bench_py_as_the_driver_launches_it_for_two_gpus():
        '2', '--master-addr', '127.0.0.1', '--master-port', str(port),
        os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
        '--size', '4096', '3000', '--iterate', '120', '--cpu-seconds', '2',
-       '--cpu-baseline-at-all-n'],
+       '--cpu-baseline-at-all-n', '--full'],
       capture_output=True, text=True, timeout=600,
       env=dict(os.environ, SODA_DIST_BACKEND='gloo', OMP_NUM_THREADS='2'))
   assert r.returncode == 0, r.stderr[-2000:]
@@ -1685,7 +1685,7 @@ def test_bench_py_as_the_driver_launches_it_for_two_gpus():
   assert abs(d['value'] - valid / (d['ms_per_step'] * 1e-3) / 1e9) < 1e-6 * d['value']
   rf = d['roofline']
   assert rf['kernel'].startswith('jacobi2d_fused_k') and 0 < rf['frac'] < 1.5
-  # with --cpu-baseline-at-all-n the CPU figure stands beside this point of the curve too
+  # with --full --cpu-baseline-at-all-n the CPU figure stands beside this point of the curve too
   # (by default it is on the N = 1 line only): rank 0 times the oracle port on the whole
   # grid AFTER the timed region, the others wait
   cpu = d['cpu_baseline']
@@ -1843,15 +1843,15 @@ def test_bench_py_one_rank_group_over_real_rccl():
 
 
 def test_bench_py_headline_line_carries_the_other_single_gpu_configs():
-  """The driver's own command (`python bench.py --steps 2 --warmup 1`) prints the headline
-  workload and, under config.other_configs, BASELINE configs 2, 3 and 5 timed on the same
-  device in the same process ("plus cfg 2, 3, 5 single-point numbers")."""
+  """`python bench.py --steps 2 --warmup 1 --full` prints the headline workload and, under
+  config.other_configs, BASELINE configs 2, 3 and 5 timed on the same device in the same
+  process ("plus cfg 2, 3, 5 single-point numbers")."""
   import subprocess
   import sys
   from conftest import ROOT
   r = subprocess.run(
       [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1',
-       '--cpu-seconds', '0'], capture_output=True, text=True, timeout=900,
+       '--cpu-seconds', '0', '--full'], capture_output=True, text=True, timeout=900,
       env={k: v for k, v in os.environ.items()
            if k not in ('SODA_DIST_BACKEND', 'RANK', 'WORLD_SIZE', 'LOCAL_RANK')})
   assert r.returncode == 0, r.stderr[-2000:]
@@ -1877,6 +1877,48 @@ def test_bench_py_headline_line_carries_the_other_single_gpu_configs():
     assert rf['bound'] in ('hbm', 'valu') and 0 < rf['frac'] <= 1.0
     assert rf['frac_algorithmic'] > 0 and rf['kernel_avg_us'] * rf['kernel_launches'] \
         <= 1.001 * o['ms'] * 1e3
+
+
+def test_bench_py_plain_run_times_its_steps_and_dumps_their_outputs(tmp_path):
+  """A plain run (no --full) prints the headline figures and nothing that takes runs of its
+  own (roofline, other configs, CPU baseline); --steps sets the timed steps, and
+  --dump-outputs writes the output of the last one - whole at this size: the CPU oracle's
+  answer on the same seeded input inside the valid box, zero outside it."""
+  import subprocess
+  import sys
+  from conftest import ROOT
+  import bench
+  dims, iterate = [1000, 700], 30
+  r = subprocess.run(
+      [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1',
+       '--size'] + [str(n) for n in dims] + ['--iterate', str(iterate),
+                                             '--dump-outputs', str(tmp_path)],
+      capture_output=True, text=True, timeout=600,
+      env={k: v for k, v in os.environ.items()
+           if k not in ('SODA_DIST_BACKEND', 'RANK', 'WORLD_SIZE', 'LOCAL_RANK')})
+  assert r.returncode == 0, r.stderr[-2000:]
+  lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
+  assert len(lines) == 1, r.stdout[-2000:]
+  d = json.loads(lines[0])
+  assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0
+  assert d['metric'] == 'gcell_updates_per_s' and d['higher_is_better'] is True
+  assert 'roofline' not in d and 'cpu_baseline' not in d
+  assert 'other_configs' not in d['config']
+  spec = gpu_util.load_spec('jacobi2d', iterate=iterate)
+  assert d['config']['launches_per_step'] == sum(
+      int(part.split('x')[0]) for part in d['config']['depth_schedule'].split('+'))
+  from soda_hip.codegen import spec as specmod
+  valid = specmod.valid_cells(spec, dims, iterate)
+  assert abs(d['value'] - valid / (d['ms_per_step'] * 1e-3) / 1e9) < 1e-6 * d['value']
+  got = np.load(tmp_path / (spec['outputs'][0] + '.npy'))
+  assert got.dtype == np.float32 and got.shape == tuple(reversed(dims))
+  orc = oracle('jacobi2d')
+  want = orc.run(bench.make_input(spec, dims), iterate=iterate)[spec['outputs'][0]]
+  sl = orc.valid_slices(tuple(dims), iterate)
+  assert np.array_equal(got[sl], want[sl])
+  outside = np.ones(got.shape, bool)
+  outside[sl] = False
+  assert outside.any() and not got[outside].any()
 
 
 def test_denormals_signed_zeros_and_infinities():

@@ -6,7 +6,7 @@ out=${1:-gpurun_out/stream_tune.log}
 echo "# box $(hostname) $(date -u +%H:%M)" >> $out
 for app in blur sobel2d jacobi2d; do
   for mode in --no-tune ""; do
-    SODA_HIP_TUNING=1 SODA_HIP_DEBUG=1 python3 bench.py --app $app --size 16384 16384 --iterate 1 --steps 30 --warmup 10 \
+    SODA_HIP_TUNING=1 SODA_HIP_DEBUG=1 python3 bench.py --app $app --size 16384 16384 --iterate 1 --steps 30 --warmup 10 --full \
         --cpu-seconds 0 $mode 2> /tmp/stream_tune.err | python3 -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
