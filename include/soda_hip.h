@@ -297,7 +297,13 @@ typedef struct soda_hip_timing {
  * The outputs are then defined on the box shrunk by soda_hip_plan_margins(
  * iterate).  Stands in for the clEnqueueTask of the generated host
  * (host.py:775-790) plus the FPGA kernel itself (hls_kernel.py:12-103).
- * Asynchronous on `stream`. */
+ * Asynchronous on `stream`.
+ * Pointers: element alignment suffices (arrays sub-allocated from a pool at 4, 20, 36 ...
+ * bytes into a 64-byte piece are as good as allocations of their own).
+ * This memory contract - in[j] bit-identical afterwards, no byte outside an array
+ * touched - is tested per kernel family, generator form and box edge in
+ * tests/test_gpu_memory_contract.py (arrays back to back between guard bands,
+ * tests/gpu_util.py), for soda_hip_run_slab with world = 1 as well. */
 int soda_hip_sweep(soda_hip_plan* plan, void* const* in, void* const* out,
                    const int64_t dims[SODA_HIP_MAX_DIMS], int iterate,
                    const int32_t* valid_lo, const int32_t* valid_hi,

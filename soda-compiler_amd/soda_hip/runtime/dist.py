@@ -659,6 +659,17 @@ def make_plan(static, dims, rank, world, r_lo, r_hi, exchange, iterate):
   return RecutPlan(dims, rank, world, r_lo, r_hi, exchange, iterate)
 
 
+def storage_rows(static, dims, rank, world, r_lo, r_hi, exchanges, iterate):
+  """Rows (extent of the slowest dimension) the shared a / b / c arrays of bench_main need
+  on this rank so that every plan it may set up fits: each exchange period under the
+  chosen cut AND under the static cut, which a failed self-check falls back to whatever
+  the command line said (on the middle ranks of three or more the static cut's slab, own
+  rows + two ghost regions, is the larger one).  --static-cut never leaves the static cut."""
+  cuts = (True,) if static else (False, True)
+  return max(make_plan(cut, dims, rank, world, r_lo, r_hi, e, iterate).local_extent
+             for e in sorted(set(exchanges)) for cut in cuts)
+
+
 def run_plan(engine, plan, arrays, iterate, margins_of, dist, schedule=None,
              ghosts_ready=False):
   if isinstance(plan, RecutPlan):
@@ -845,10 +856,9 @@ def bench_main(args, open_program, make_input, per_iteration_updates,
     # builds its slab (own rows + ITS ghost rows) as a view of three arrays sized for
     # the deepest ghost regions
     own_rows = torch.from_numpy(make_input(spec, dims, rows=(start, stop))[0]).to(dev)
-    extents = [make_plan(cut, dims, rank, world, r_lo, r_hi, e, args.iterate).local_extent
-               for e in sorted({e for e, _ in pairs})
-               for cut in ((static,) if cut_given else (False, True))]
-    full_shape = tuple(reversed(dims[:-1] + [max(extents)]))
+    rows = storage_rows(static, dims, rank, world, r_lo, r_hi, {e for e, _ in pairs},
+                        args.iterate)
+    full_shape = tuple(reversed(dims[:-1] + [rows]))
     storage = [torch.zeros(full_shape, dtype=tdt, device=dev) for _ in range(3)]
     engine = HipEngine(program, torch)
     margin_table = specmod.iteration_margins(spec, args.iterate)
@@ -864,6 +874,11 @@ def bench_main(args, open_program, make_input, per_iteration_updates,
       plan = make_plan(static if static_cut is None else static_cut, dims, rank, world,
                        r_lo, r_hi, exchange, args.iterate)
       a, b, c = (t[:plan.local_extent] for t in storage)
+      # (a slice of a shorter tensor is silently shorter; the engine sweeps
+      # plan.local_dims through raw pointers)
+      assert all(t.shape[0] == plan.local_extent for t in (a, b, c)), (
+          'slab storage holds %d rows, the %s cut at exchange %d needs %d' % (
+              storage[0].shape[0], type(plan).__name__, plan.exchange, plan.local_extent))
       a[plan.ghost_lo:plan.ghost_lo + plan.own].copy_(own_rows)
       order = (StreamSchedule if overlapped else TimedSerialSchedule)(
           torch, host_sync=backend != 'nccl')

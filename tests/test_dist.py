@@ -281,3 +281,52 @@ def test_all_ranks_choose_the_same_exchange(tmp_path):
   slowest = [max(a, b) * 1e3 for a, b in zip(*times)]
   assert [r['ms'] for r in got[0]['table']] == pytest.approx(slowest)
   assert (got[0]['chosen']['exchange'], got[0]['chosen']['overlapped']) == (192, False)
+
+
+# (dims, reach lo, reach hi, iterate, exchange periods): the multi-rank cases of this file
+# and of the GPU suite, and the two full-size benchmark configurations with the periods
+# exchange_candidates gives them
+_STORAGE_CASES = [
+    ([16384, 16384], 1, 1, 1000, [24, 48, 96, 144, 192]),
+    ([512, 512, 512], 1, 1, 200, [4, 8, 16, 32]),
+    ([4096, 1500], 1, 1, 60, [12, 24, 48, 60]),
+    ([40, 96], 1, 1, 12, [4]), ([40, 120], 1, 1, 13, [6]), ([72, 128], 1, 1, 30, [8]),
+    ([52, 50, 64], 1, 1, 24, [4]), ([26, 24, 32], 1, 1, 10, [4]),
+    ([70, 75], 0, 2, 6, [2, 3]),                 # one-sided window (blur)
+]
+
+
+@pytest.mark.parametrize('world', [3, 4, 8])
+@pytest.mark.parametrize('dims,r_lo,r_hi,iterate,exchanges', _STORAGE_CASES)
+@pytest.mark.parametrize('static', [False, True])
+def test_slab_storage_covers_every_cut_the_run_may_fall_back_to(world, dims, r_lo, r_hi,
+                                                                iterate, exchanges, static):
+  """bench_main's shared a / b / c arrays (storage_rows) hold plan.local_extent rows of
+  every plan setup() may build: each period under the chosen cut and under the static
+  cut of the fallback after a failed self-check.  Sized from the re-cut alone they were
+  too short on middle ranks (16384^2 x 1000, E = 96, 4 ranks: 4288 rows needed, 4240
+  there; 512^3 on 8 ranks: 96 against 92) and the sweep ran past the allocation."""
+  for rank in range(world):
+    try:
+      rows = sdist.storage_rows(static, dims, rank, world, r_lo, r_hi, exchanges, iterate)
+    except ValueError:        # slabs thinner than the reach: refused before any storage
+      continue
+    for e in exchanges:
+      for cut in ((True,) if static else (False, True)):
+        need = sdist.make_plan(cut, dims, rank, world, r_lo, r_hi, e, iterate).local_extent
+        assert rows >= need, (world, rank, dims, e, 'static' if cut else 'recut', rows, need)
+
+
+def test_slab_storage_of_the_two_recorded_overruns():
+  """The figures of the finding itself: the static cut's slab on a middle rank against
+  what the re-cut alone asks for."""
+  recut = sdist.make_plan(False, [16384, 16384], 1, 4, 1, 1, 96, 1000).local_extent
+  fallback = sdist.make_plan(True, [16384, 16384], 1, 4, 1, 1, 96, 1000).local_extent
+  assert (recut, fallback) == (4240, 4288)
+  assert sdist.storage_rows(False, [16384, 16384], 1, 4, 1, 1, [96], 1000) == 4288
+  small = [sdist.make_plan(False, [512, 512, 512], 3, 8, 1, 1, e, 200).local_extent
+           for e in (4, 8, 16, 32)]
+  big = [sdist.make_plan(True, [512, 512, 512], 3, 8, 1, 1, e, 200).local_extent
+         for e in (4, 8, 16, 32)]
+  assert max(big) > max(small)
+  assert sdist.storage_rows(False, [512, 512, 512], 3, 8, 1, 1, [4, 8, 16, 32], 200) == max(big)

@@ -1733,6 +1733,17 @@ def test_bench_py_refuses_a_run_whose_ghost_rows_arrive_wrong(cut):
 
 
 def test_bench_py_falls_back_to_the_conservative_configuration():
+  _bench_py_falls_back(2)
+
+
+def test_bench_py_falls_back_to_the_conservative_configuration_on_three_ranks():
+  """The same with a MIDDLE rank, whose static slab (own rows + two ghost regions) is
+  larger than anything the re-cut asked for: the arrays the fallback sweeps must have been
+  sized for it (dist.storage_rows; setup() asserts it)."""
+  _bench_py_falls_back(3)
+
+
+def _bench_py_falls_back(world):
   """When the self-check fails for the configuration the warm-up chose, bench.py checks the
   most conservative one in its place - static cut, serial order - and goes on with it only
   if THAT is bit-exact, saying so on the line.  Here only the re-cut's exchanges are damaged
@@ -1747,9 +1758,9 @@ def test_bench_py_falls_back_to_the_conservative_configuration():
   port = s.getsockname()[1]
   s.close()
   r = subprocess.run(
-      [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
-       '--master-addr', '127.0.0.1', '--master-port', str(port),
-       os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '0',
+      [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node',
+       str(world), '--master-addr', '127.0.0.1', '--master-port', str(port),
+       os.path.join(ROOT, 'bench.py'), '--gpus', str(world), '--steps', '1', '--warmup', '0',
        '--size', '4096', '1500', '--iterate', '60', '--cpu-seconds', '0', '--no-tune',
        '--recut'], capture_output=True, text=True, timeout=600,
       env=dict(os.environ, SODA_DIST_BACKEND='gloo', OMP_NUM_THREADS='2', SODA_HIP_TUNING='1',
