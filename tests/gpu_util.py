@@ -62,6 +62,79 @@ def random_inputs(spec, shape, seed=SEED, small_ints=False):
   return out
 
 
+# ---- full-width operands ------------------------------------------------------------------
+#
+# random_inputs' floats lie in [0, 1) with float32's mantissa whatever the type (the low
+# dword of every such double is 0), and the random programs' integers in 0..199 (the high
+# dword of every such int64 is 0): half of an 8-byte element is constant, no narrow
+# element has its top bit set, and every float sum adds positive numbers of one magnitude.
+# wide_inputs fills every bit of the element and mixes signs and exponents.
+
+WIDE_EXPONENTS = 12        # floats: sign * m * 2^e, e in -12 .. 12
+WIDE_EXPONENTS_HALF = 10   # _Float16 (largest finite 65504): e in -10 .. 10
+
+
+def wide_array(dtype, shape, rng, exponents=None):
+  """Integers: uniform over the whole range of the type.  Floats: sign * m * 2^e with a
+  random sign, m uniform in [1, 2) on the type's OWN mantissa grid (52 / 23 / 10 bits -
+  not float32 widened) and e uniform in -exponents .. exponents; every value is exact in
+  the type, none is zero, subnormal, inf or NaN."""
+  dt = np.dtype(dtype)
+  if dt.kind != 'f':
+    info = np.iinfo(dt)
+    return rng.integers(info.min, info.max, size=shape, dtype=dt, endpoint=True)
+  if exponents is None:
+    exponents = WIDE_EXPONENTS_HALF if dt.itemsize == 2 else WIDE_EXPONENTS
+  bits = np.finfo(dt).nmant
+  m = 1.0 + rng.integers(0, 1 << bits, size=shape).astype(np.float64) * 2.0 ** -bits
+  e = rng.integers(-exponents, exponents + 1, size=shape)
+  sign = np.where(rng.integers(0, 2, size=shape) == 1, -1.0, 1.0)
+  v = np.ldexp(m, e) * sign          # exact in float64: m has at most 52 fraction bits
+  out = v.astype(dt)
+  assert np.array_equal(out.astype(np.float64), v)
+  return out
+
+
+def wide_inputs(spec, shape, seed=SEED, exponents=None):
+  """One array per input of the program, of the input's type (wide_array); the same
+  arrays for the same seed."""
+  rng = np.random.default_rng(seed)
+  return [wide_array(specmod.NUMPY_NAME[t['c_type']], shape, rng, exponents)
+          for t in spec['inputs']]
+
+
+# Programs whose float results overflow on +-12 (a condition on the inputs, not on the
+# product: tests/test_operand_ranges.py, test_wide_floats_do_not_overflow, holds every
+# float program and sample to finite results on these spans).  Keys: sample names and the
+# keys of tests/golden/random_programs.json.  At most five.
+NARROWED_EXPONENTS = {
+    # the output holds f r1, r1 of degree 6 in r0 = 4.9 u f: |u|, |f| < 2^13 would need
+    # 1e100.  +-12 and +-8 overflow on the CPU, +-7 stays a factor 5 below FLT_MAX on one
+    # seed, +-6 four orders of magnitude
+    'denoise2d': 6,
+}
+
+
+def wide_inputs_of(key, spec, shape, seed=SEED):
+  """wide_inputs with the exponent span of program `key`."""
+  return wide_inputs(spec, shape, seed, NARROWED_EXPONENTS.get(key))
+
+
+# The oracle the full-width cases are held to.  On full-range integers a signed sum or
+# product overflows, which plain C++ leaves undefined - the plain oracle has no answer
+# there (hence random_inputs' small_ints for sobel2d).  The product, however, PROMISES
+# two's-complement wrap: every kernel is compiled with -fwrapv (codegen/kernel.py,
+# runtime/host.py; DESIGN.md section 2), so the oracle gets the same flag and integer
+# arithmetic modulo 2^n is defined on both sides for any input.  -fwrapv only gives a
+# meaning to what was undefined: wherever no signed overflow occurs this oracle equals the
+# plain one (tests/test_operand_ranges.py holds -O2 against -O0 under it).
+WRAP_FLAGS = ('-O2', '-fwrapv')
+
+
+def make_wrap_oracle(spec, opt='-O2'):
+  return make_oracle(spec, flags=(opt,) + WRAP_FLAGS[1:])
+
+
 # ---- the sweep's memory contract (include/soda_hip.h: soda_hip_sweep, soda_hip_run_slab) ----
 #
 #   in[j]   never written;   out[j]  any cell may be written, nothing outside the array;

@@ -143,14 +143,17 @@ def skews_for(mode, n, itemsize):
 
 
 def hold(prog, orc, shape, iterate, mode, family=None, depth=None, split=None, seed=None,
-         edge=None, small_ints=False):
+         edge=None, small_ints=False, inputs=None):
   """One guarded run: box == oracle bit for bit, guards intact, inputs unchanged, and the
   launches included the family (and depth) the case names.  `edge`: 'first' / 'last' -
-  the box must start on element 0 / end on the array's last element."""
+  the box must start on element 0 / end on the array's last element.  `inputs`: the
+  caller's operands instead of gpu_util.random_inputs (tests/test_gpu_operand_ranges.py)."""
   spec = prog.spec
   dims = tuple(reversed(shape))
-  inputs = gpu_util.random_inputs(spec, shape, seed=seed or gpu_util.SEED + sum(shape),
-                                  small_ints=small_ints)
+  if inputs is None:
+    inputs = gpu_util.random_inputs(spec, shape, seed=seed or gpu_util.SEED + sum(shape),
+                                    small_ints=small_ints)
+  assert all(a.shape == tuple(shape) for a in inputs)
   if split:
     prog.set_split(dims, iterate, split)
   try:

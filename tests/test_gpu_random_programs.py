@@ -5,6 +5,7 @@ streaming pipeline), fan-in and fan-out DAGs, `let`s, casts, integer division,
 several inputs, 2-D and 3-D, fused and per-stage kernels, every depth split; and
 integer programs over the remaining operators of the grammar (% & | ^ comparisons
 && || unary - ~ !, non-decimal literals)."""
+import concurrent.futures
 import json
 import os
 
@@ -30,19 +31,28 @@ with open(os.path.join(GOLDEN, 'random_manifest.json')) as f:
   REFERENCE = {v['key']: (k, v) for k, v in json.load(f).items() if k.endswith('.npz')}
 
 
+WIDE = 'oracle, full-width operands'
+
+
 def run_case(key, shape, rng, **gen):
   """One random program through the HIP back end (hiprtc), every depth split:
   (a) on the inputs of the REFERENCE's own run of this program, against the
   reference's result (tests/golden/random.<key>.npz, made by `make_golden.py
   --random`; 28 of the 56 programs - the others have a window that excludes the
   store point, for which the reference's loops leave the arrays or do not compile);
-  (b) on a larger grid against the CPU oracle."""
+  (b) on a larger grid against the CPU oracle;
+  (c) on that grid with full-width, mixed-sign operands against the oracle built with
+  -fwrapv (what the kernels are built with: signed overflow wraps)."""
   entry = PROGRAMS[key]
   text, iterate = entry['text'], entry['iterate']
   stencil = frontend.loads(text)
   spec = specmod.spec_from_stencil(stencil)
-  src, table = kernel.generate(spec, **gen)
-  prog = host.open_program(source=src, spec=spec)
+  # the two checkers compile (g++) beside the kernels (hiprtc), not after them
+  with concurrent.futures.ThreadPoolExecutor(2) as pool:
+    plain_orc = pool.submit(gpu_util.make_oracle, spec)
+    wrap_orc = pool.submit(gpu_util.make_wrap_oracle, spec)
+    src, table = kernel.generate(spec, **gen)
+    prog = host.open_program(source=src, spec=spec)
   fused = [k['depth'] for k in table if k['kind'] == 'fused']
   cases = []
   if key in REFERENCE:
@@ -51,7 +61,7 @@ def run_case(key, shape, rng, **gen):
     ins = [np.ascontiguousarray(data['in_' + t['name']]) for t in spec['inputs']]
     cases.append((ins, {n: data['out_' + n] for n in spec['outputs']},
                   'reference fixture'))
-  orc = gpu_util.make_oracle(spec)
+  orc = plain_orc.result()
   inputs = []
   for t in spec['inputs']:
     dt = np.dtype(specmod.NUMPY_NAME[t['c_type']])
@@ -60,6 +70,13 @@ def run_case(key, shape, rng, **gen):
     else:
       inputs.append(rng.integers(0, 200, size=shape).astype(dt))
   cases.append((inputs, orc.run(inputs, iterate=iterate), 'oracle'))
+  # (c) on the same grid with every bit of the element in use - integers over the whole
+  # range of the type, floats of both signs over 25 binades at the type's own mantissa
+  # (the inputs of (a) and (b) leave one dword of every 8-byte element constant) - against
+  # the oracle built with -fwrapv, as the kernels are (gpu_util.make_wrap_oracle)
+  wide = gpu_util.wide_inputs_of(key, spec, shape, seed=gpu_util.SEED + len(key))
+  cases.append((wide, wrap_orc.result().run(wide, iterate=iterate), WIDE))
+  nonempty = set()            # outputs whose box held cells in the 'oracle' case
   for ins, wants, what in cases:
     sl = orc.valid_slices(tuple(reversed(ins[0].shape)), iterate)
     for max_depth in sorted({0, 1, -1} if fused else {-1}):
@@ -75,13 +92,20 @@ def run_case(key, shape, rng, **gen):
           own = tuple(slice(-blo[d], max(-blo[d], got.shape[::-1][d] - bhi[d]))
                       for d in reversed(range(spec['dim'])))
           same = np.array_equal(got[own], want[own], equal_nan=True)
-          assert what != 'oracle' or got[own].size > 0, (key, name)
+          assert what not in ('oracle', WIDE) or got[own].size > 0, (key, name, what)
           if what == 'reference fixture':
             same = same and np.array_equal(got, want, equal_nan=True)
         elif want[sl].size == 0:
+          # (the full-width case does not hide behind an empty box the oracle case had not)
+          assert what != WIDE or name not in nonempty, (key, name, what)
           continue
         else:
+          if what == 'oracle':
+            nonempty.add(name)
           same = np.array_equal(got[sl], want[sl], equal_nan=True)
+        if what == WIDE and want.dtype.kind == 'f':
+          # inputs that overflowed would compare inf with inf, NaN with NaN
+          assert np.isfinite(want[own if len(spec['outputs']) > 1 else sl]).all(), (key, name)
         assert same, '%s `%s` vs %s, max_depth %d (fused depths %s)\n%s' % (
             key, name, what, max_depth, fused, text)
   prog.close()

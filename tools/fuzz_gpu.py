@@ -2,8 +2,9 @@
 """Fuzzing run on the GPU box: fresh seeds of the random-program generators of the
 tests (tests/random_programs.py), HIP path (hiprtc) against the CPU oracle for every
 depth split.  Not a test: a hunt; a failing program goes into the committed families.
-usage: fuzz_gpu.py family first_seed count [generator options k=v,...]
-(family: plain ops struct cube deep)"""
+usage: fuzz_gpu.py [--wide] family first_seed count [generator options k=v,...]
+(family: plain ops struct cube deep; --wide: full-width, mixed-sign operands -
+gpu_util.wide_inputs - against the oracle built with -fwrapv)"""
 import sys as _sys
 if len(_sys.argv) > 1 and _sys.argv[1] in ('-h', '--help'):   # usage = the text above
   print(__doc__)
@@ -16,12 +17,15 @@ import traceback
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'soda-compiler_amd'), os.path.join(ROOT, 'tests')]
 import numpy as np
+import gpu_util
 import random_programs as rp
 from soda_hip import frontend
 from soda_hip.codegen import kernel, spec as specmod
 from soda_hip.runtime import host
 from oracle import soda_oracle
 
+wide = '--wide' in sys.argv
+sys.argv = [a for a in sys.argv if a != '--wide']
 family, first, count = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
 gen = {'plain': rp.random_program, 'deep': rp.random_program, 'ops': rp.operator_program,
        'struct': rp.structure_program, 'cube': rp.cube_program}[family]
@@ -57,11 +61,14 @@ for seed in range(first, first + count):
       gen_options = {k: v for k, v in gen_options.items() if k != 'blk_pairs'}
     src, table = kernel.generate(spec, **gen_options)
     prog = host.open_program(source=src, spec=spec)
-    orc = soda_oracle.Oracle(spec, build_dir=scratch)
+    orc = soda_oracle.Oracle(spec, build_dir=scratch,
+                             flags=gpu_util.WRAP_FLAGS if wide else ('-O2',))
     inputs = []
     for t in spec['inputs']:
       dt = np.dtype(specmod.NUMPY_NAME[t['c_type']])
-      if dt.kind == 'f':
+      if wide:
+        inputs.append(gpu_util.wide_array(dt, tuple(shape), rng))
+      elif dt.kind == 'f':
         inputs.append((rng.random(tuple(shape), dtype=np.float32) + np.float32(0.5)).astype(dt))
       else:
         inputs.append(rng.integers(0, 200, size=tuple(shape)).astype(dt))

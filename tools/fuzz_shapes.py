@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Fuzzing run on the GPU box: the prebuilt sample programs on random array shapes
 (tiny, ragged, around the kernels' smallest-array limits) and iteration counts,
-against the CPU oracle.  usage: fuzz_shapes.py first_seed count"""
+against the CPU oracle.  usage: fuzz_shapes.py [--wide] first_seed count
+(--wide: full-width, mixed-sign operands - gpu_util.wide_inputs - against the oracle built
+with -fwrapv; sobel2d then runs on full-range uint16)"""
 import sys as _sys
 if len(_sys.argv) > 1 and _sys.argv[1] in ('-h', '--help'):   # usage = the text above
   print(__doc__)
@@ -15,7 +17,9 @@ import numpy as np
 import gpu_util
 from soda_hip.codegen import spec as specmod
 
-first, count = int(sys.argv[1]), int(sys.argv[2])
+wide = '--wide' in sys.argv
+argv = [a for a in sys.argv if a != '--wide']
+first, count = int(argv[1]), int(argv[2])
 apps = ['jacobi2d', 'blur', 'seidel2d', 'sobel2d', 'denoise2d', 'skew2d', 'jacobi3d',
         'heat3d', 'denoise3d']
 progs, oracles = {}, {}
@@ -26,7 +30,8 @@ for seed in range(first, first + count):
   app = apps[int(rng.integers(0, len(apps)))]
   if app not in progs:
     progs[app] = gpu_util.open_prebuilt(app)
-    oracles[app] = gpu_util.make_oracle(progs[app].spec)
+    oracles[app] = (gpu_util.make_wrap_oracle if wide else gpu_util.make_oracle)(
+        progs[app].spec)
   prog, orc = progs[app], oracles[app]
   spec = prog.spec
   dim = spec['dim']
@@ -45,7 +50,10 @@ for seed in range(first, first + count):
   else:
     hi = 40 if rng.random() < 0.3 else 180
     shape = tuple(int(rng.integers(1, hi)) for _ in range(3))
-  inputs = gpu_util.random_inputs(spec, shape, seed=seed, small_ints=(app == 'sobel2d'))
+  if wide:
+    inputs = gpu_util.wide_inputs(spec, shape, seed=seed)
+  else:
+    inputs = gpu_util.random_inputs(spec, shape, seed=seed, small_ints=(app == 'sobel2d'))
   max_depth = int(rng.choice([0, 0, 0, -1, 1, 2, 4, 8, 12, 16, 20]))
   try:
     prog.set_max_depth(max_depth)
