@@ -244,7 +244,19 @@ typedef struct soda_hip_args {
   int64_t box_hi[SODA_HIP_MAX_DIMS];
   int64_t param[4]; /* param[0]: outer-dimension rows per workgroup, chosen per
                        launch so that the grid fills the chip in whole rounds;
-                       param[1], param[2], param[3]: see soda_hip_kernel.xcd_tiles */
+                       param[1], param[2], param[3]: 3-D kernels: see
+                       soda_hip_kernel.xcd_tiles.  Fused 2-D kernels of programs with
+                       two or more outputs: each output is defined on a box of its own
+                       and [box_lo, box_hi) is the INTERSECTION of those boxes; the
+                       three words, read as one string of 192 bits, hold 32 bits per
+                       output j (word 1 + j / 2, bits 32 (j % 2) up):
+                         lo0 | lo1 << 8 | hi0 << 16 | hi1 << 24,
+                       each 0..255: output j is stored on
+                         [box_lo[d] - lo_d, box_hi[d] + hi_d), d = 0, 1.
+                       That is room for 6 outputs; programs with more keep their
+                       per-stage kernels.  The grid covers the union of the boxes
+                       (the box widened by the largest extra per side).  All zero
+                       = every output on [box_lo, box_hi). */
 } soda_hip_args;
 
 /* ---- plan -------------------------------------------------------------------
@@ -329,8 +341,11 @@ int soda_hip_plan_schedule(soda_hip_plan* plan,
                            int32_t* kernel_index, double* est_us, int capacity,
                            int* n_launches);
 
-/* Restricts fused kernels to depth <= max_depth (0 = no limit); for tests and
- * tuning. */
+/* Restricts fused kernels to depth <= max_depth (0 = no limit, < 0 = per-stage
+ * kernels only); for tests and tuning.  The fused kernels of programs with several
+ * outputs (param[1..3] above) are not in the default schedule until they have been
+ * measured: at 0 such a program runs per stage unless a split is set for the
+ * arguments; a limit > 0 admits them. */
 int soda_hip_plan_set_max_depth(soda_hip_plan* plan, int max_depth);
 
 /* Optional: finds the split of `iterate` into fused depths that runs fastest on THIS

@@ -353,12 +353,45 @@ std::array<int64_t, 5> stream_key(const soda_hip_plan* plan, int k, const soda_h
   return key;
 }
 
-int make_launch(const soda_hip_plan* plan, int k, const soda_hip_args& args,
+// Fused 2-D kernels of programs with several outputs (kernel_fields2d.py) store output j
+// on a box of its own: the launch's box - the intersection of the outputs' boxes -
+// widened by the four extras of soda_hip_args.param[1..3] (include/soda_hip.h).
+constexpr int kMaxExtraOutputs = 6;     // 3 words x 64 bits / (4 x 8 bits per output)
+constexpr int kMaxExtra = 255;
+
+bool takes_output_extras(const soda_hip_plan* plan, const soda_hip_kernel& desc) {
+  return desc.kind == SODA_HIP_KERNEL_FUSED && plan->prog.dim == 2 && plan->prog.n_outputs > 1;
+}
+
+// extras of output j: {lo x, lo y, hi x, hi y}
+void unpack_extras(const soda_hip_args& a, int j, int64_t* ex) {
+  const uint64_t word = (uint64_t)a.param[1 + j / 2] >> (32 * (j % 2));
+  for (int i = 0; i < 4; ++i) ex[i] = (word >> (8 * i)) & 0xff;
+}
+
+// the union of the outputs' boxes: what the strips and chunks of such a launch cover
+void widen_to_union(const soda_hip_plan* plan, soda_hip_args* a) {
+  int64_t most[4] = {0, 0, 0, 0};
+  for (int j = 0; j < plan->prog.n_outputs; ++j) {
+    int64_t ex[4];
+    unpack_extras(*a, j, ex);
+    for (int i = 0; i < 4; ++i) most[i] = std::max(most[i], ex[i]);
+  }
+  for (int d = 0; d < 2; ++d) {
+    a->box_lo[d] -= most[d];
+    a->box_hi[d] += most[2 + d];
+  }
+}
+
+int make_launch(const soda_hip_plan* plan, int k, const soda_hip_args& launch_args,
                 Launch* out, bool* empty) {
   const soda_hip_kernel& desc = plan->kernels[k];
   const int dim = plan->prog.dim;
   out->kernel = k;
-  out->args = args;
+  out->args = launch_args;
+  // the grid is sized by `args`: the launch's box, or the union of the outputs' boxes
+  soda_hip_args args = launch_args;
+  if (takes_output_extras(plan, desc)) widen_to_union(plan, &args);
   out->est_us = 0;
   out->lds_bytes = 0;
   *empty = false;
@@ -677,6 +710,17 @@ int build_schedule(soda_hip_plan* plan, void* const* in, void* const* out,
   });
   bool fused_ok = !fused.empty() && plan->kernels[fused.back()].depth == 1;
   if (plan->max_depth < 0) fused_ok = false;  // force per-stage kernels
+  if (fused_ok && plan->max_depth == 0 && !plan->tuning &&
+      takes_output_extras(plan, plan->kernels[fused.back()])) {
+    // The fused kernels over several fields have not been timed on an MI355X yet
+    // (profiles/r07_fields.txt), so no depth of theirs has earned its place in the default
+    // schedule: they run where the caller asks for them, with a depth limit
+    // (soda_hip_plan_set_max_depth > 0) or a split (soda_hip_plan_set_split, _tune).
+    std::array<int64_t, 5> key;
+    for (int d = 0; d < 4; ++d) key[d] = d < p.dim ? dims[d] : 1;
+    key[4] = iterate;
+    if (plan->tuned_split.find(key) == plan->tuned_split.end()) fused_ok = false;
+  }
 
   if (fused_ok) {
     // Split of `iterate` into the available depths: the cheapest one under the
@@ -804,6 +848,33 @@ int build_schedule(soda_hip_plan* plan, void* const* in, void* const* out,
       }
       int rc = check_box_inside(plan, a, reach_lo, reach_hi);
       if (rc) return rc;
+      if (takes_output_extras(plan, desc)) {
+        // every output on ITS box of level done + depth, as extras against the hull
+        if (p.n_outputs > kMaxExtraOutputs)
+          return fail(SODA_HIP_ERR_INTERNAL, "kernel %s: %d outputs, the launch arguments "
+                      "carry the boxes of %d", desc.name, p.n_outputs, kMaxExtraOutputs);
+        const std::vector<Box>& level = plan->boxes[done + desc.depth - 1];
+        for (int j = 0; j < p.n_outputs; ++j) {
+          const Box& o = level[p.output_tensor[j]];
+          const int64_t ex[4] = {mlo[0] + o.lo[0], mlo[1] + o.lo[1], mhi[0] - o.hi[0],
+                                 mhi[1] - o.hi[1]};
+          soda_hip_args own = a;      // the widened box must lie inside the array as well
+          for (int d = 0; d < 2; ++d) {
+            if (ex[d] < 0 || ex[d] > kMaxExtra || ex[2 + d] < 0 || ex[2 + d] > kMaxExtra)
+              return fail(SODA_HIP_ERR_INTERNAL, "kernel %s: output %d is %lld / %lld cells "
+                          "wider than the launch's box in dimension %d (limit %d)", desc.name,
+                          j, (long long)ex[d], (long long)ex[2 + d], d, kMaxExtra);
+            own.box_lo[d] -= ex[d];
+            own.box_hi[d] += ex[2 + d];
+          }
+          const int32_t none[SODA_HIP_MAX_DIMS] = {0, 0, 0, 0};
+          rc = check_box_inside(plan, own, none, none);
+          if (rc) return rc;
+          const uint64_t word = (uint64_t)ex[0] | (uint64_t)ex[1] << 8 |
+                                (uint64_t)ex[2] << 16 | (uint64_t)ex[3] << 24;
+          a.param[1 + j / 2] |= (int64_t)(word << (32 * (j % 2)));
+        }
+      }
       Launch l;
       bool empty;
       rc = make_launch(plan, seq[i], a, &l, &empty);

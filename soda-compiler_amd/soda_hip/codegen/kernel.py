@@ -19,8 +19,8 @@ import subprocess
 import tempfile
 
 from .. import __version__
-from . import (kernel_common, kernel_stage, kernel_stream2d, kernel_stream2d_wp,
-               kernel_stream3d, kernel_stream3d_blk, kernel_stream3d_wp)
+from . import (kernel_common, kernel_fields2d, kernel_stage, kernel_stream2d,
+               kernel_stream2d_wp, kernel_stream3d, kernel_stream3d_blk, kernel_stream3d_wp)
 from . import spec as specmod
 
 DEFAULT_MAX_DEPTH = 12
@@ -110,6 +110,10 @@ PACKED_3D_LIGHT_WEIGHT = 10
 # operations per cell, is VALU-bound at depth 1 and loses 19 % to the narrower
 # aligned strips; blur 20, sobel2d 28, jacobi2d 5 gain)
 ALIGN_FULL_MAX_WEIGHT = 40
+
+# depths of the multi-field form (kernel_fields2d)
+FIELDS_DEPTHS = (1, 2, 4, 8)
+FIELDS_OPTIONS = ('skip_fill', 'vgpr_budget', 'max_period', 'waves_per_eu')
 
 # generator options of the fused 2-D forms that `generate` passes through:
 # those both forms understand, and those only the wave-pipelined form has
@@ -236,6 +240,13 @@ def fused_depths(spec, max_depth):
     # 12 is the measured sweet spot for 4-byte 5-point programs on MI355X
     # (two waves per SIMD at ~200 VGPRs; 16 drops to one wave, 8 is HBM-bound)
     return [d for d in (1, 2, 4, 8, 12)
+            if d <= max_depth and d <= max(1, spec['iterate'])]
+  if spec['dim'] == 2 and kernel_stream2d.multi_field(spec) and \
+      len(spec['outputs']) <= kernel_fields2d.MAX_OUTPUTS:
+    # several fields, output j feeding input j (kernel_fields2d): every field's windows
+    # of every iteration share one wavefront's registers - 8 is as deep as two- and
+    # three-field programs go before the budget check refuses
+    return [d for d in FIELDS_DEPTHS
             if d <= max_depth and d <= max(1, spec['iterate'])]
   return [1]
 
@@ -364,7 +375,24 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   text, table = kernel_stage.emit(spec)
   parts.append(text)
   notes = []
-  if fused and spec['dim'] == 2:
+  if fused and spec['dim'] == 2 and kernel_stream2d.multi_field(spec):
+    wanted = list(fused_depths(spec, max_depth))
+    if depths is not None:
+      wanted = sorted(set([1] + list(depths)))
+    for depth in wanted:
+      try:
+        ftext, entry = kernel_fields2d.emit(
+            spec, depth, cols=cols if cols else default_cols(spec),
+            chunk_rows=chunk_rows or 256, prefetch=3 if prefetch is None else prefetch,
+            **{k: v for k, v in fused_options.items() if k in FIELDS_OPTIONS})
+      except kernel_stream2d.NotFusable as e:
+        notes.append('depth %d not fused: %s' % (depth, e))
+        if depth == 1:      # the scheduler needs depth 1: without it, per-stage kernels
+          break
+        continue
+      parts.append(ftext)
+      table.append(annotate_cost(entry, spec))
+  elif fused and spec['dim'] == 2:
     wanted = list(fused_depths(spec, max_depth))
     # one level deeper for programs the packed wave-pipelined form covers: it
     # is the only form with the registers for it and, fed through the LDS ring,

@@ -54,14 +54,25 @@ class Instance:
     self.final = False          # last iteration's output: goes to HBM
 
 
-def build_pipeline(spec, depth, prefetch):
+def multi_field(spec):
+  """Iterated programs over several fields: as many outputs as inputs (two or more),
+  output j of input j's type - the DSL's `iterate` rule beyond one array."""
+  types = specmod.tensor_c_types(spec)
+  return len(spec['inputs']) == len(spec['outputs']) >= 2 and all(
+      t['c_type'] == types[o] for t, o in zip(spec['inputs'], spec['outputs']))
+
+
+def build_pipeline(spec, depth, prefetch, fields=False):
+  """fields: the caller stores every output (kernel_fields2d) - multi_field programs
+  are taken, and the last iteration's instance of EVERY output is marked final."""
   if spec['dim'] != 2:
     raise NotFusable('stream2d handles 2-D programs')
-  if len(spec['outputs']) != 1:
-    raise NotFusable('stream2d handles single-output programs')
   ins = [t['name'] for t in spec['inputs']]
-  if depth > 1 and len(ins) != 1:
-    raise NotFusable('depth > 1 needs one input feeding one output')
+  if not (fields and multi_field(spec)):
+    if len(spec['outputs']) != 1:
+      raise NotFusable('stream2d handles single-output programs')
+    if depth > 1 and len(ins) != 1:
+      raise NotFusable('depth > 1 needs one input feeding one output')
   types = specmod.tensor_c_types(spec)
   for name, ctype in types.items():
     if specmod.ELEM_SIZE[ctype] not in (1, 2, 4, 8):
@@ -85,7 +96,8 @@ def build_pipeline(spec, depth, prefetch):
       if len(ins) == len(spec['outputs']):
         current[i] = current[o]
   final = current[spec['outputs'][0]]
-  final.final = True
+  for o in spec['outputs'] if fields else spec['outputs'][:1]:
+    current[o].final = True
   # lags: a reader can produce row y once every row y+dy it reads exists;
   # rows of loaded inputs count as existing `prefetch` steps after their load
   for inst in insts:
@@ -123,8 +135,8 @@ def geometry(spec, depth, cols, chunk_rows, align='none'):
   256/0 382 us - alignment is worth more than the extra halo reads for the
   kernels that HBM bounds."""
   margins = specmod.iteration_margins(spec, depth)
-  if len(spec['inputs']) == 1 and len(spec['outputs']) == 1:
-    lo, hi = margins[-1]
+  if (len(spec['inputs']) == 1 and len(spec['outputs']) == 1) or multi_field(spec):
+    lo, hi = margins[-1]     # the hull over all fields, composed over `depth` iterations
   else:
     lo, hi = margins[0]
   elem = specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
@@ -151,6 +163,78 @@ def geometry(spec, depth, cols, chunk_rows, align='none'):
   return dict(x_lo=lo[0], x_hi=hi[0], y_lo=lo[1], y_hi=hi[1],
               halo_lo=halo_lo, halo_hi=halo_hi, w_out=w_out,
               chunk_rows=chunk_rows, origin_align=origin_align)
+
+
+def rotation_period(insts, max_period):
+  """Rotation period: the row loop is unrolled `period` times so that every
+  window's "shift" is a renaming; each keep must divide it.  Keeping MORE rows
+  than needed is always legal, so keeps are rounded up to divisors of the
+  period that costs the fewest registers (jacobi2d: 6,3,3.. -> period 6, no
+  padding; denoise2d: 6,7,1,2,3.. would need lcm 42 -> period 8 with 8,8,1,2,4).
+  Sets every instance's `keep`; returns the period."""
+  best = None
+  for candidate in range(1, max_period + 1):
+    if max(inst.keep for inst in insts) > candidate:
+      continue
+    divisors = [d for d in range(1, candidate + 1) if candidate % d == 0]
+    padded = [min(d for d in divisors if d >= inst.keep) if inst.keep else 0
+              for inst in insts]
+    cost = (sum(k * max(1, specmod.ELEM_SIZE[i.c_type] // 4)
+                for k, i in zip(padded, insts)), candidate)
+    if best is None or cost < best[0]:
+      best = (cost, candidate, padded)
+  if best is None:
+    raise NotFusable('windows of up to %d rows exceed the rotation period limit %d'
+                     % (max(inst.keep for inst in insts), max_period))
+  for inst, keep in zip(insts, best[2]):
+    inst.keep = keep
+  return best[1]
+
+
+def estimated_vgprs(insts, cols):
+  """Every retained row costs `cols` VGPRs per lane (2 x for 8-byte types), the edge
+  columns of seam-free strips along with them; past ~224 the kernel drops below two
+  waves per SIMD and then spills."""
+  return sum(inst.keep * (cols + sum(getattr(inst, 'edges', {}).values())) *
+             max(1, specmod.ELEM_SIZE[inst.c_type] // 4) for inst in insts) + \
+      4 * cols + 16
+
+
+def set_first_steps(insts, y_lo):
+  """First step at which each instance's row can matter.  Rows of a final
+  output below the chunk's first row y0 are never stored, so walking back
+  through the readers gives, per instance, how many rows below y0 it is still
+  needed (`below`); it then first matters at step lag + y_lo - below.  During
+  the pipeline fill the generated prologue skips instances before that step."""
+  below = {id(inst): 0 for inst in insts if inst.final}
+  for inst in reversed(insts):
+    need = below.get(id(inst))
+    if need is None:
+      continue
+    for src, rel, _ in inst.reads:
+      below[id(src)] = max(below.get(id(src), -10**9), need - rel[1])
+  for inst in insts:
+    inst.first_step = max(0, inst.lag + y_lo - below.get(id(inst), 0))
+
+
+def slot(inst, u, back):
+  """physical row of `inst`'s window holding its `back`-th newest row while
+  unrolled copy `u` runs (after `inst` produced this step's row)."""
+  return (u - back) % inst.keep
+
+
+def lane_operand(reader, src, rel, u, c, cols):
+  """Cell (c + rel[0]) of the row of `src` that `reader` reads at rel: a register of
+  the lane's own window, or the neighbouring lane's through a DPP wave shift."""
+  back = reader.lag - src.lag - rel[1]
+  assert 0 <= back < src.keep, (reader.ident, src.ident, rel, back, src.keep)
+  row = '%s[%d]' % (src.ident, slot(src, u, back))
+  j = c + rel[0]
+  if 0 <= j < cols:
+    return '%s[%d]' % (row, j)
+  if j < 0:
+    return 'from_lane_below(%s[%d])' % (row, cols + j)
+  return 'from_lane_above(%s[%d])' % (row, j - cols)
 
 
 def kernel_name(spec, depth):
@@ -219,50 +303,12 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
                              '%s across lanes itself' % (inst.tensor, src.tensor))
           for side in ('lo', 'hi'):
             src.edges[side] = max(src.edges[side], inst.edges[side])
-  # Rotation period: the row loop is unrolled `period` times so that every
-  # window's "shift" is a renaming; each keep must divide it.  Keeping MORE rows
-  # than needed is always legal, so keeps are rounded up to divisors of the
-  # period that costs the fewest registers (jacobi2d: 6,3,3.. -> period 6, no
-  # padding; denoise2d: 6,7,1,2,3.. would need lcm 42 -> period 8 with 8,8,1,2,4).
-  best = None
-  for candidate in range(1, max_period + 1):
-    if max(inst.keep for inst in insts) > candidate:
-      continue
-    divisors = [d for d in range(1, candidate + 1) if candidate % d == 0]
-    padded = [min(d for d in divisors if d >= inst.keep) if inst.keep else 0
-              for inst in insts]
-    cost = (sum(k * max(1, specmod.ELEM_SIZE[i.c_type] // 4)
-                for k, i in zip(padded, insts)), candidate)
-    if best is None or cost < best[0]:
-      best = (cost, candidate, padded)
-  if best is None:
-    raise NotFusable('windows of up to %d rows exceed the rotation period limit %d'
-                     % (max(inst.keep for inst in insts), max_period))
-  period = best[1]
-  for inst, keep in zip(insts, best[2]):
-    inst.keep = keep
-  # register budget: every retained row costs C VGPRs per lane (2C for 8-byte
-  # types); past ~224 the kernel drops below two waves per SIMD and then spills
-  est_vgprs = sum(inst.keep * (cols + sum(inst.edges.values())) *
-                  max(1, specmod.ELEM_SIZE[inst.c_type] // 4) for inst in insts) + \
-      4 * cols + 16
+  period = rotation_period(insts, max_period)
+  est_vgprs = estimated_vgprs(insts, cols)
   if est_vgprs > vgpr_budget:
     raise NotFusable('depth %d would need about %d VGPRs (budget %d)'
                      % (depth, est_vgprs, vgpr_budget))
-  # First step at which each instance's row can matter.  Rows of the final
-  # output below the chunk's first row y0 are never stored, so walking back
-  # through the readers gives, per instance, how many rows below y0 it is still
-  # needed (`below`); it then first matters at step lag + y_lo - below.  During
-  # the pipeline fill the generated prologue skips instances before that step.
-  below = {id(final): 0}
-  for inst in reversed(insts):
-    need = below.get(id(inst))
-    if need is None:
-      continue
-    for src, rel, _ in inst.reads:
-      below[id(src)] = max(below.get(id(src), -10**9), need - rel[1])
-  for inst in insts:
-    inst.first_step = max(0, inst.lag + geo['y_lo'] - below.get(id(inst), 0))
+  set_first_steps(insts, geo['y_lo'])
   name = kernel_name(spec, depth)
   C = cols
   L = final.lag
@@ -360,11 +406,6 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
   prologue_steps = -(-prologue_steps // period) * period if skip_fill else 0
   emit_line('  i64 n = 0;')
 
-  def slot(inst, u, back):
-    """physical row of `inst`'s window holding its `back`-th newest row while
-    unrolled copy `u` runs (after `inst` produced this step's row)."""
-    return (u - back) % inst.keep
-
   def operand(reader, src, rel, u, c):
     back = reader.lag - src.lag - rel[1]
     assert 0 <= back < src.keep, (reader.ident, src.ident, rel, back, src.keep)
@@ -379,9 +420,7 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
             row, C + j, src.ident, slot(src, u, back), -j - 1)
       return 'from_lane_above_or(%s[%d], edge_hi_%s[%d][%d])' % (
           row, j - C, src.ident, slot(src, u, back), j - C)
-    if j < 0:
-      return 'from_lane_below(%s[%d])' % (row, C + j)
-    return 'from_lane_above(%s[%d])' % (row, j - C)
+    return lane_operand(reader, src, rel, u, c, C)
 
   def emit_body(guarded, calm=False):
     """calm: the steady-state copy - every row loaded lies inside the array, every
