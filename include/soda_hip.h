@@ -159,7 +159,7 @@ typedef struct soda_hip_kernel {
                             scheduler skips it otherwise */
   /* Cost figures of a streaming kernel, from the kernel printer (0 = none): the
    * scheduler prices every fused depth with them and splits `iterate` into the
-   * cheapest sequence of launches (soda_hip.cpp: step_seconds). */
+   * cheapest sequence of launches (csrc/schedule.cpp: step_seconds). */
   int32_t step_valu;  /* VALU issue cycles ONE workgroup (all its wavefronts
                          together) spends per streamed row / plane */
   int32_t step_bytes; /* HBM bytes one workgroup loads + stores per step */

@@ -45,7 +45,7 @@ def output_extras(spec, done, depth):
   """Per output, (lo_x, lo_y, hi_x, hi_y): by how many cells its box after `done` +
   `depth` iterations is wider than the intersection of all outputs' boxes - what the
   launcher packs into param[1..3] for the launch that takes level `done` to `done` +
-  `depth` (soda_hip.cpp, build_schedule, computes the same from its own boxes)."""
+  `depth` (csrc/schedule.cpp, pack_output_extras, computes the same from its own boxes)."""
   boxes = specmod.iteration_boxes(spec, done + depth)[-1]
   mlo, mhi = specmod.iteration_margins(spec, done + depth)[-1]
   out = []
@@ -262,7 +262,7 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
   emit_line('  const int wave = __builtin_amdgcn_workitem_id_x() >> 6;')
   emit_line('  const %s_boxes b = %s_output_boxes(a);' % (name, name))
   # the union of the outputs' boxes is what strips and chunks cover (the launcher sizes
-  # the grid by the same rule: soda_hip.cpp, make_launch)
+  # the grid by the same rule: csrc/schedule.cpp, make_launch)
   emit_line('  i64 lo_x = b.lo_x[0], lo_y = b.lo_y[0], hi_x = b.hi_x[0], hi_y = b.hi_y[0];')
   for j in range(1, len(finals)):
     emit_line('  if (b.lo_x[%d] < lo_x) lo_x = b.lo_x[%d]; if (b.lo_y[%d] < lo_y) lo_y = '

@@ -62,8 +62,8 @@ def emit(spec):
     lines.append('  if (x >= a.box_hi[0]) return;')
     # rows / planes: one per workgroup.  Boxes with more than 65535 rows or planes
     # (the limit of grid.y / grid.z) are launched with the rows and planes folded
-    # into one index n = wgid_y + wgid_z * grid.y (param[0] = 1, soda_hip.cpp:
-    # make_launch); everything else keeps the direct mapping.
+    # into one index n = wgid_y + wgid_z * grid.y (param[0] = 1, csrc/schedule.cpp:
+    # fold_rows); everything else keeps the direct mapping.
     if dim == 2:
       lines.append('  const i64 y = a.box_lo[1] + __builtin_amdgcn_workgroup_id_y() + '
                    '(i64)__builtin_amdgcn_workgroup_id_z() * __builtin_amdgcn_grid_size_y();')

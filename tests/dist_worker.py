@@ -24,8 +24,8 @@ class OracleEngine:
 
   def __init__(self, spec, launch_depth=0):
     """launch_depth = D > 0: behave like a sweep split into launches of D
-    iterations whose destinations alternate as libsoda_hip's do (soda_hip.cpp:
-    build_schedule): unless final_only, every second launch counted from the end
+    iterations whose destinations alternate as libsoda_hip's do (csrc/schedule.cpp:
+    destination): unless final_only, every second launch counted from the end
     writes ITS level's (larger) box into dst too."""
     self.spec = spec
     self.oracle = soda_oracle.Oracle(spec)

@@ -1,5 +1,5 @@
 // TEST-ONLY stand-in for librccl.so: the handful of entry points the slab drivers
-// use (soda_hip.cpp: soda_hip_run_slab; the generated <app>_multi_gpu), implemented
+// use (csrc/slab.cpp: soda_hip_run_slab; the generated <app>_multi_gpu), implemented
 // for "ranks" that are host threads of ONE process sharing ONE GPU.  RCCL itself
 // refuses two ranks on a device, and no multi-GPU box is available to the GPU
 // tests, so without this the world > 1 code below the C ABI would never execute.

@@ -640,7 +640,7 @@ def test_edge_tiles_cover_every_box_exactly_once():
   start and width: the stored ranges tile [box_lo, box_hi) exactly, every stored column is
   one the tile's (possibly moved) window computes validly, and no box takes more tiles
   than under the old rule (start at box_lo rounded down, every tile stores tile[0])."""
-  def launcher(lo, hi, tile, slack, align=16):          # soda_hip.cpp: make_launch
+  def launcher(lo, hi, tile, slack, align=16):          # csrc/schedule.cpp: edge_slack_tiles
     x0 = (lo + slack) - (lo + slack) % align
     if x0 >= hi:
       x0 = lo - lo % align

@@ -204,7 +204,7 @@ def margins_of(spec, iterate):
 
 
 def edge_tiles(k, lo, hi):
-  """The launcher's placement of a row of tiles of a kernel with edge_slack (soda_hip.cpp,
+  """The launcher's placement of a row of tiles of a kernel with edge_slack (schedule.cpp,
   launch geometry, dimension 0) for a box [lo, hi): (first tile's origin, tiles)."""
   slack, align, tile = k['edge_slack'], k['origin_align'], k['tile'][0]
   x0 = (lo + slack) - (lo + slack) % align

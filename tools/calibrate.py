@@ -12,7 +12,7 @@ that deep kernel:
   * cache-resident array, <= 1 workgroup/CU   -> step_ns_one  (forced long chunks)
   * array far beyond the Infinity Cache       -> stream_gbps
   * an array in between (about twice the cache) -> fade_lo_mib / fade_hi_mib: the
-    footprints between which the HBM term of the price fades in (soda_hip.cpp:
+    footprints between which the HBM term of the price fades in (csrc/schedule.cpp:
     step_seconds), placed so that the model reproduces this launch
   * shallow kernels (the ones HBM bounds): the streaming launch again under a few chunk
     lengths and caps on workgroups per CU -> stream_chunk (+ stream_wgs_per_cu) when one
@@ -37,7 +37,7 @@ SIZES = {   # (cache-resident, streaming, in between) extents per dimension
     2: (3072, 16384, 8192),
     3: (256, 512, 384),
 }
-FADE_DEFAULT = (128, 512)      # MiB; soda_hip.cpp: kCacheResidentMiB, kStreamingMiB
+FADE_DEFAULT = (128, 512)      # MiB; csrc/schedule.cpp: kCacheResidentMiB, kStreamingMiB
 # chunk lengths tried for the streaming launch of kernels up to this depth
 STREAM_CHUNKS = (8, 12, 16, 24, 32, 48, 64, 96)
 STREAM_SWEEP_MAX_DEPTH = {2: 4, 3: 2}
