@@ -8,11 +8,22 @@ it is designed for a GPU instead of an FPGA dataflow region.
 
 The unit holds
   * one per-stage kernel per stage (kernel_stage.py), always;
-  * fused kernels of depth 1, 2, 4, ... (kernel_stream2d.py) when the program
-    is in their scope;
+  * the fused kernels of the program's family, at the depths selected below:
+      multi-field 2-D   kernel_fields2d
+      single-array 2-D  kernel_stream2d (one strip per wavefront) or, deep,
+                        kernel_stream2d_wp (wave-pipelined)
+      3-D, depth 1-2    kernel_stream3d (one tile per wavefront)
+      3-D chains        kernel_stream3d_blk (block form) and / or
+                        kernel_stream3d_wp (wave-pipelined);
   * `soda_hip_meta`, JSON describing the program and the kernel table, which
     libsoda_hip.so reads back from the loaded blob.
+
+generate() is the driver: one function per family (FAMILIES) selects forms, depths and
+options, form_options() says which options a form receives.
 """
+import hashlib
+import inspect
+import json
 import os
 import re
 import subprocess
@@ -275,8 +286,6 @@ def calibration_key(entry, spec):
   a change of the generator that changes the kernel's shape makes its measurement
   stale (the scheduler then falls back to the model) until tools/calibrate.py has
   run again."""
-  import hashlib
-  import json
   # (edge_slack changes which tiles a launch has, not what a workgroup's step costs: the
   # streamed loop is the same text with and without it)
   shape = {k: v for k, v in entry.items()
@@ -289,7 +298,6 @@ def calibration_key(entry, spec):
 def calibration():
   global _calibration
   if _calibration is None:
-    import json
     try:
       with open(CALIBRATION_FILE) as f:
         _calibration = json.load(f).get('kernels', {})
@@ -343,7 +351,6 @@ def annotate_cost(entry, spec):
 def prefixed_options(options, prefix, emit):
   """The `<prefix>name=value` entries of `options` as keyword arguments of `emit`;
   a name `emit` does not take is an error, not a silently ignored knob."""
-  import inspect
   known = inspect.signature(emit).parameters
   out = {}
   for key, value in options.items():
@@ -355,12 +362,351 @@ def prefixed_options(options, prefix, emit):
   return out
 
 
+
+# Which of generate()'s `**fused_options` a kernel form receives: the one place that says so.
+# Tools pass one option set across programs of different families, so what a form does not
+# receive is dropped in silence, while a name that reaches an emit() which does not take it
+# is a TypeError.  fields2d and stream2d_wp receive the names listed for them; stream2d and
+# stream3d every name but those held back for the other forms (a name nobody knows therefore
+# ends in their emit()); stream3d_blk and stream3d_wp the `blk_` / `wp_` names, checked
+# against the emit() by prefixed_options.
+FORM_OPTIONS = dict(
+    fields2d=lambda k: k in FIELDS_OPTIONS,
+    stream2d=lambda k: k not in WP_ONLY_OPTIONS and k != 'nt',
+    stream2d_wp=lambda k: k in SHARED_2D_OPTIONS + WP_ONLY_OPTIONS,
+    stream3d=lambda k: not k.startswith(('wp_', 'blk_')) and
+    k not in ('deep3d', 'deep3d_from', 'nontemporal'))
+PREFIXED_FORMS = dict(stream3d_blk=('blk_', kernel_stream3d_blk.emit),
+                      stream3d_wp=('wp_', kernel_stream3d_wp.emit))
+
+
+def form_options(form, options):
+  if form in PREFIXED_FORMS:
+    return prefixed_options(options, *PREFIXED_FORMS[form])
+  return {k: v for k, v in options.items() if FORM_OPTIONS[form](k)}
+
+
+def first_fusable(spec, depth, attempts):
+  """(result, None) of the first `emit(spec, depth, **kwargs)` among the `(emit, kwargs)`
+  of `attempts` that does not raise NotFusable; (None, the LAST error) when all do."""
+  error = None
+  for emit, kwargs in attempts:
+    try:
+      return emit(spec, depth, **kwargs), None
+    except kernel_stream2d.NotFusable as e:
+      error = e
+  return None, error
+
+
+class Request:
+  """What generate() was asked for, normalised once; every family function receives it."""
+
+  def __init__(self, spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
+               options):
+    self.spec, self.depths, self.options = spec, depths, options
+    self.max_depth = DEFAULT_MAX_DEPTH if max_depth is None else max_depth
+    self.cols, self.prefetch = cols, prefetch       # as given: a form may have its own default
+    # columns per lane, rows per chunk and rows in flight of the 2-D strips
+    self.strip = dict(cols=cols if cols else default_cols(spec),
+                      chunk_rows=chunk_rows or 256,
+                      prefetch=3 if prefetch is None else prefetch)
+    self.groups = WAVE_GROUPS if wave_groups is None else wave_groups
+    self.single_array = len(spec['inputs']) == len(spec['outputs']) == 1
+    if spec['dim'] == 3:
+      self.default_depths = [d for d in (1, 2) if d <= max(1, spec['iterate'])] \
+          if self.single_array else [1]
+    else:
+      self.default_depths = list(fused_depths(spec, self.max_depth))
+    # the program is an iteration chain the fused forms can deepen (anything else gets
+    # depth 1 only, whatever `depths` asks for)
+    self.chain = len(self.default_depths) > 1
+
+
+def fields2d_kernels(req, notes):
+  """Multi-field 2-D programs: kernel_fields2d at each depth."""
+  spec = req.spec
+  if spec['dim'] != 2 or not kernel_stream2d.multi_field(spec):
+    return
+  wanted = req.default_depths
+  if req.depths is not None:
+    wanted = sorted(set([1] + list(req.depths)))
+  for depth in wanted:
+    found, error = first_fusable(spec, depth, [
+        (kernel_fields2d.emit, dict(req.strip, **form_options('fields2d', req.options)))])
+    if found is None:
+      notes.append('depth %d not fused: %s' % (depth, error))
+      if depth == 1:      # the scheduler needs depth 1: without it, per-stage kernels
+        return
+      continue
+    yield found
+
+
+def stream2d_depths(req):
+  spec, wanted = req.spec, list(req.default_depths)
+  # one level deeper for programs the packed wave-pipelined form covers: it
+  # is the only form with the registers for it and, fed through the LDS ring,
+  # the only one that gains from it (jacobi2d 16384^2: depth 12 single-wave
+  # 46.0 us per iteration, depth 16 packed + ring 39.5)
+  if (req.chain and req.max_depth >= DEFAULT_MAX_DEPTH and req.single_array and
+      req.groups == -1 and kernel_stream2d_wp.packable(spec)):
+    wanted += [d for d in PACKED_DEEP_DEPTHS if spec['iterate'] >= d]
+  if req.depths is not None:
+    wanted = sorted(set([1] + [d for d in req.depths if req.chain or d == 1]))
+  return wanted
+
+
+def stream2d_single(req, depth, strip, notes):
+  """The single-wave kernel of this depth (kernel_stream2d), or None with a note."""
+  # the memory-bound depths store around the caches when a launch's box
+  # does not fit the Infinity Cache (kernel_stream2d.emit: nontemporal)
+  options = dict({'nontemporal': 4} if depth <= NT_AUTO_MAX_DEPTH_2D else {},
+                 **form_options('stream2d', req.options))
+  # ... and where no STAGE is read across lanes (depth 1 of the samples) their
+  # strips do not overlap at all (align='exact': whole 128-byte lines in and
+  # out, the seam columns from one extra vector load per row and side)
+  aligns = ['exact', 'full'] if strip.get('align') == 'full' else \
+      [options.pop('align', None) or strip['align']]
+  attempts = []
+  for how in aligns:
+    shape = dict(strip, align=how)
+    if how == 'exact' and req.prefetch is None:
+      # six rows in flight per wavefront (two workgroups per CU on the arrays
+      # that matter, soda_hip_kernel.stream_wgs_per_cu)
+      shape['prefetch'] = EXACT_PREFETCH
+    attempts.append((kernel_stream2d.emit, dict(shape, **options)))
+  single, error = first_fusable(req.spec, depth, attempts)
+  if single is None:
+    notes.append('depth %d not fused: %s' % (depth, error))
+  return single
+
+
+# The wave-pipelined form at this depth: always when asked for by a number of wavefronts;
+# when left to choose (WAVE_GROUPS, -1), where the single-wave form does not fit or needs
+# more than AUTO_WP_VGPRS registers, and for packable programs from PACKED_FROM_DEPTH on
+# (the measurements are at those constants).
+def want_piped(req, depth, single):
+  return depth >= WAVE_PIPELINE_MIN_DEPTH and (
+      req.groups > 1 or (req.groups == -1 and (
+          single is None or single[1]['est_vgprs'] > AUTO_WP_VGPRS or
+          (depth >= PACKED_FROM_DEPTH and kernel_stream2d_wp.packable(req.spec)))))
+
+
+# A chosen ring kernel a few registers over four workgroups per CU (128 VGPRs) is built a
+# second time under that cap (stream2d_piped says how, per form).
+def squeeze(req, options, entry):
+  return (req.groups == -1 and options.get('ring') and
+          'waves_per_eu' not in options and
+          128 < entry['est_vgprs'] <= AUTO_WP_SQUEEZE_VGPRS)
+
+
+def stream2d_piped(req, depth, strip, notes):
+  """The wave-pipelined kernel of this depth (kernel_stream2d_wp), or None with a note."""
+  spec, groups = req.spec, req.groups
+  options = form_options('stream2d_wp', req.options)
+  if groups == -1:
+    options.setdefault('vgpr_budget', AUTO_WP_BUDGET)
+    lane_bytes = strip['cols'] * specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
+    if lane_bytes == 16:
+      # input rows through the LDS ring: no prefetch registers (see
+      # kernel_stream2d_wp.emit); needs 16-byte lanes
+      options.setdefault('ring', AUTO_WP_RING)
+    # packable programs: one 512-column strip per wavefront, its two halves
+    # sharing register pairs (pairs=2; jacobi2d depth 16 per launch on
+    # 16384^2: 597 us against 627 us for two 256-column strips, pairs=1)
+    options.setdefault('pairs', 0 if not kernel_stream2d_wp.packable(spec)
+                       else 2 if options.get('ring') else 1)
+    if depth > PACKED_DEEP_DEPTH and options['pairs'] == 2:
+      # 5-6 levels per wavefront: three workgroups per CU (168 VGPRs;
+      # depth 24 left alone takes 174 = two per CU: 34.1 vs 33.2 us per
+      # iteration at 16384^2)
+      options.setdefault('waves_per_eu', PACKED_DEEP_WAVES_PER_EU)
+  emit = kernel_stream2d_wp.emit
+  piped, error = first_fusable(spec, depth, [
+      (emit, dict(strip, groups=AUTO_WP_GROUPS if groups == -1 else groups, **options))])
+  if piped is not None and squeeze(req, options, piped[1]):
+    capped = None
+    if options.get('pairs') == 2 and options['ring'] == AUTO_WP_RING \
+        and 'max_period' not in options:
+      # a few registers over four workgroups per CU: cap them at 128.  In
+      # the wide form that pays only together with a 12-slot ring (10 rows
+      # in flight) unrolled over 12 rows: jacobi2d depth 16, 16384^2, per
+      # launch 578 us uncapped with ring 6, 830 us capped with ring 6,
+      # 560 us capped with ring 12.
+      capped = dict(options, ring=2 * AUTO_WP_RING, max_period=2 * AUTO_WP_RING)
+    elif not options.get('pairs'):
+      # the scalar form: let the compiler spill the few registers over the cap
+      # (not the two-strip packed form: its scalar DPP adds then spill 45
+      # registers and lose 60 %)
+      capped = options
+    if capped is not None:
+      # (a capped kernel that does not fuse leaves the first one, and a note)
+      again, error = first_fusable(spec, depth, [
+          (emit, dict(strip, groups=AUTO_WP_GROUPS, waves_per_eu=4, **capped))])
+      piped = again or piped
+  if error is not None:
+    notes.append('depth %d not wave-pipelined: %s' % (depth, error))
+  return piped
+
+
+def stream2d_kernels(req, notes):
+  """Single-array 2-D programs: per depth the wave-pipelined kernel, else the single-wave."""
+  spec = req.spec
+  if spec['dim'] != 2 or kernel_stream2d.multi_field(spec):
+    return
+  for depth in stream2d_depths(req):
+    strip = dict(req.strip)
+    if 'align' not in req.options:
+      # (deeper kernels keep the widest strips: strips on 64-byte pieces,
+      # align='store64', gain 1.8 % on cfg2 in short runs and LOSE 1.3 % under the
+      # bench protocol's sustained load - 0.949 vs 0.961 ms, three alternating pairs
+      # in one call; cfg4 29.17 vs 29.22 ms)
+      strip['align'] = 'full' if (
+          depth <= ALIGN_FULL_MAX_DEPTH and
+          arithmetic_weight(spec) <= ALIGN_FULL_MAX_WEIGHT) else 'none'
+    single = piped = None
+    if req.groups <= 1 or depth < WAVE_PIPELINE_MIN_DEPTH:
+      single = stream2d_single(req, depth, strip, notes)
+    if want_piped(req, depth, single):
+      piped = stream2d_piped(req, depth, strip, notes)
+      if piped is None and single is None and req.groups > 1:
+        # asked for by a number of wavefronts and refused: the single-wave form after all
+        single, error = first_fusable(spec, depth, [
+            (kernel_stream2d.emit, dict(strip, **form_options('stream2d', req.options)))])
+        if single is None:
+          notes.append('depth %d not fused: %s' % (depth, error))
+    if piped is not None or single is not None:
+      yield piped if piped is not None else single
+
+
+def stream3d_kernels(req, notes):
+  """3-D programs, depths 1 and 2: one tile per wavefront (kernel_stream3d)."""
+  spec, cols = req.spec, req.cols
+  if spec['dim'] != 3:
+    return
+  wanted = req.default_depths
+  if req.depths is not None:
+    wanted = sorted(set([1] + list(req.depths))) if req.chain else [1]
+  for depth in wanted:
+    options = form_options('stream3d', req.options)
+    # (rows, columns) per lane: the tallest tile the register file allows (taller
+    # tiles waste less on the y halo).  Programs with several live tensors
+    # (denoise3d, lowered to g and output over the inputs f and u) fit with one
+    # column per lane: 12 rows (156 VGPRs, three wavefronts per SIMD) before 16
+    # (235 VGPRs, two) - denoise3d per sweep at 256^3 / 512^3: 160 / 971 us against
+    # 200 / 999 us, the two per-stage launches 165 / 1281 us
+    narrow = [] if cols or len(spec['inputs']) == len(spec['outputs']) else \
+        [(12, 1), (16, 1)]      # (iteration chains go deep in the forms below)
+    shapes = [(options.pop('rows'), cols or 2)] if 'rows' in options else \
+        [(16, cols or 2), (12, cols or 2)] + narrow
+    options.setdefault('nt', 4)
+    found, error = first_fusable(spec, depth, [
+        (kernel_stream3d.emit, dict(options, rows=rows, cols=lane_cols))
+        for rows, lane_cols in shapes])
+    if found is None:
+      notes.append('depth %d not fused: %s' % (depth, error))
+    else:
+      yield found
+
+
+def deep3d_block(req, depth, notes):
+  """The block form of this depth (kernel_stream3d_blk), or None with a note."""
+  # block form: all levels in every wavefront, edge rows through LDS
+  # (kernel_stream3d_blk).  Named <app>_fused_k<d>b; with 'both' it ships
+  # NEXT TO the wave-pipelined kernel and the run-time picks per launch
+  spec = req.spec
+  given = form_options('stream3d_blk', req.options)
+  heavy = arithmetic_weight(spec) > PACKED_3D_LIGHT_WEIGHT
+  ring_forms = [dict(BLOCK_3D_RING_OPTIONS)]
+  if heavy and kernel_stream2d_wp.packable(spec):
+    # heavy plain-float programs: packed pair-rows first (heat3d 512^3 x20,
+    # block form alone, clocks warm: 1.76 ms plain, 1.42 packed - 13.2 k instead
+    # of 22.6 k VALU instructions per unrolled loop, 254 VGPRs without spills
+    # now that the ring took the prefetch registers; a hand-ordered scalar
+    # instruction stream, round 3's kernel_asm, reached 1.49 and is gone)
+    # (and exact store ranges: whole 64-byte pieces cost this kernel 3 %,
+    # heat3d 512^3 x20 1.37 -> 1.41 ms, where they gain jacobi3d's 2 %)
+    ring_forms.insert(0, dict(BLOCK_3D_RING_OPTIONS, pairs=1, wide_stores=0))
+  bases = [BLOCK_3D_OPTIONS] if 'prefetch' in given or 'ring' in given else \
+      ring_forms + [BLOCK_3D_OPTIONS]
+  found, error = first_fusable(spec, depth, [
+      (kernel_stream3d_blk.emit, dict(base, **given)) for base in bases])
+  if found is None:
+    notes.append('depth %d not in block form: %s' % (depth, error))
+  return found
+
+
+def deep3d_piped(req, depth, notes):
+  """The wave-pipelined kernel of this depth (kernel_stream3d_wp), or None with a note."""
+  spec = req.spec
+  options = form_options('stream3d_wp', req.options)
+  options.setdefault('groups', min(depth * len(spec['stages']), 4))
+  # (no non-temporal stores here: heat3d 512^3 x20 with this form alone 2.09 ms
+  # without, 2.12 ms with wp_nt=4)
+  if options.get('split', 2) == 2 and not options.get('loader') and \
+      options.get('rows', 16) % 2 == 0 and kernel_stream2d_wp.packable(spec):
+    # packed pair-rows (v_pk_*_f32) for programs heavy enough on arithmetic:
+    # heat3d (weight 15) 459 us per launch scalar, 383-440 us packed at the
+    # 230 VGPRs the compiler asks for (629 us capped at three workgroups per
+    # CU: 360 spilled registers).  Light programs are bounded by memory and
+    # keep the scalar form at three workgroups per CU: jacobi3d (weight 7),
+    # cfg5 with the offline compiler: 6.23 ms scalar, 7.43 ms packed (36
+    # spilled registers); hiprtc happens to favour the packed form (6.31 vs
+    # 6.63 ms) - the shipped code objects are built by hipcc.
+    options.setdefault('pairs', int(arithmetic_weight(spec) >
+                                    PACKED_3D_LIGHT_WEIGHT))
+    if options['pairs']:
+      options.setdefault('waves_per_eu', 0)
+  found, error = first_fusable(spec, depth, [(kernel_stream3d_wp.emit, options)])
+  if found is None:
+    notes.append('depth %d not wave-pipelined: %s' % (depth, error))
+  return found
+
+
+def deep3d_kernels(req, notes):
+  """Light 3-D iteration chains: per depth the block form, the wave-pipelined or both."""
+  spec, depths = req.spec, req.depths
+  if spec['dim'] != 3:
+    return
+  # deeper than one wavefront's registers allow: one level per wavefront
+  # The block form serves the shallow depths as well (deep3d_from=3: not): next to the
+  # single-wave kernels above, which stay for arrays below its 128 x 64 tile and for
+  # programs it does not take.  jacobi3d per launch, depth 1 / 2: 512^3 470 / 395 us
+  # single-wave, 221 / 222 us block form (one read and one write of the array at 5.3
+  # TB/s: 203 us); 256^3 67 / 65 against 33 / 35; heat3d 512^3 depth 2 464 -> 231.
+  deep_from = req.options.get('deep3d_from', 1)
+  deep = [d for d in sorted(set(depths if depths is not None else
+                                BLOCK_3D_SHALLOW_DEPTHS + DEEP_3D_DEPTHS))
+          if d >= deep_from and d <= max(1, spec['iterate'])]
+  if not (req.single_array and (
+      depths is not None or arithmetic_weight(spec) <= DEEP_3D_MAX_WEIGHT)):
+    return
+  form = req.options.get('deep3d', DEEP_3D_FORM)
+  for depth in deep:
+    if depth < 3 and form == 'wp':      # one level per wavefront needs >= 3 levels
+      continue
+    if form in ('blk', 'both'):
+      found = deep3d_block(req, depth, notes)
+      if found is not None:
+        yield found
+      # (a depth >= 3 the block form refused goes on to the wave-pipelined form,
+      # with deep3d='blk' as well)
+      if depth < 3 or (form == 'blk' and found is not None):
+        continue
+    found = deep3d_piped(req, depth, notes)
+    if found is not None:
+      yield found
+
+
+# the kernel families in the order their kernels enter the table; each yields the
+# (text, entry) of the kernels it selects for this request and appends to `notes`
+FAMILIES = (fields2d_kernels, stream2d_kernels, stream3d_kernels, deep3d_kernels)
+
+
 def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
              fused=True, depths=None, inline=True, wave_groups=None,
              **fused_options):
   """Returns (kernel text, kernel table).  `depths` overrides the default set
   of fused depths (depth 1 is always included: the scheduler needs it)."""
-  max_depth = DEFAULT_MAX_DEPTH if max_depth is None else max_depth
   # kernels are generated from the LOWERED program (pointwise-only locals folded
   # into their readers); the blob is still identified by the source program
   source = spec
@@ -375,249 +721,12 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   text, table = kernel_stage.emit(spec)
   parts.append(text)
   notes = []
-  if fused and spec['dim'] == 2 and kernel_stream2d.multi_field(spec):
-    wanted = list(fused_depths(spec, max_depth))
-    if depths is not None:
-      wanted = sorted(set([1] + list(depths)))
-    for depth in wanted:
-      try:
-        ftext, entry = kernel_fields2d.emit(
-            spec, depth, cols=cols if cols else default_cols(spec),
-            chunk_rows=chunk_rows or 256, prefetch=3 if prefetch is None else prefetch,
-            **{k: v for k, v in fused_options.items() if k in FIELDS_OPTIONS})
-      except kernel_stream2d.NotFusable as e:
-        notes.append('depth %d not fused: %s' % (depth, e))
-        if depth == 1:      # the scheduler needs depth 1: without it, per-stage kernels
-          break
-        continue
+  req = Request(spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
+                fused_options)
+  for family in FAMILIES if fused else ():
+    for ftext, entry in family(req, notes):
       parts.append(ftext)
       table.append(annotate_cost(entry, spec))
-  elif fused and spec['dim'] == 2:
-    wanted = list(fused_depths(spec, max_depth))
-    # one level deeper for programs the packed wave-pipelined form covers: it
-    # is the only form with the registers for it and, fed through the LDS ring,
-    # the only one that gains from it (jacobi2d 16384^2: depth 12 single-wave
-    # 46.0 us per iteration, depth 16 packed + ring 39.5)
-    if (len(wanted) > 1 and max_depth >= DEFAULT_MAX_DEPTH and
-        len(spec['inputs']) == len(spec['outputs']) == 1 and
-        (WAVE_GROUPS if wave_groups is None else wave_groups) == -1 and
-        kernel_stream2d_wp.packable(spec)):
-      wanted += [d for d in PACKED_DEEP_DEPTHS if spec['iterate'] >= d]
-    if depths is not None:
-      wanted = sorted(set([1] + [d for d in depths if len(wanted) > 1 or d == 1]))
-    for depth in wanted:
-      groups = WAVE_GROUPS if wave_groups is None else wave_groups
-      common = dict(cols=cols if cols else default_cols(spec),
-                    chunk_rows=chunk_rows or 256,
-                    prefetch=3 if prefetch is None else prefetch)
-      if 'align' not in fused_options:
-        # (deeper kernels keep the widest strips: strips on 64-byte pieces,
-        # align='store64', gain 1.8 % on cfg2 in short runs and LOSE 1.3 % under the
-        # bench protocol's sustained load - 0.949 vs 0.961 ms, three alternating pairs
-        # in one call; cfg4 29.17 vs 29.22 ms)
-        common['align'] = 'full' if (
-            depth <= ALIGN_FULL_MAX_DEPTH and
-            arithmetic_weight(spec) <= ALIGN_FULL_MAX_WEIGHT) else 'none'
-      single = piped = None
-      if groups <= 1 or depth < WAVE_PIPELINE_MIN_DEPTH or groups == -1:
-        # the memory-bound depths store around the caches when a launch's box
-        # does not fit the Infinity Cache (kernel_stream2d.emit: nontemporal)
-        options = dict({'nontemporal': 4} if depth <= NT_AUTO_MAX_DEPTH_2D else {},
-                       **{k: v for k, v in fused_options.items()
-                          if k not in WP_ONLY_OPTIONS and k != 'nt'})
-        # ... and where no STAGE is read across lanes (depth 1 of the samples) their
-        # strips do not overlap at all (align='exact': whole 128-byte lines in and
-        # out, the seam columns from one extra vector load per row and side)
-        aligns = ['exact', 'full'] if common.get('align') == 'full' else \
-            [options.pop('align', None) or common['align']]
-        for k, how in enumerate(aligns):
-          shape = dict(common, align=how)
-          if how == 'exact' and prefetch is None:
-            # six rows in flight per wavefront (two workgroups per CU on the arrays
-            # that matter, soda_hip_kernel.stream_wgs_per_cu)
-            shape['prefetch'] = EXACT_PREFETCH
-          try:
-            single = kernel_stream2d.emit(spec, depth, **shape, **options)
-            break
-          except kernel_stream2d.NotFusable as e:
-            if k == len(aligns) - 1:
-              notes.append('depth %d not fused: %s' % (depth, e))
-      want_piped = depth >= WAVE_PIPELINE_MIN_DEPTH and (
-          groups > 1 or (groups == -1 and (
-              single is None or single[1]['est_vgprs'] > AUTO_WP_VGPRS or
-              (depth >= PACKED_FROM_DEPTH and kernel_stream2d_wp.packable(spec)))))
-      if want_piped:
-        options = {k: v for k, v in fused_options.items()
-                   if k in SHARED_2D_OPTIONS + WP_ONLY_OPTIONS}
-        if groups == -1:
-          options.setdefault('vgpr_budget', AUTO_WP_BUDGET)
-          lane_bytes = common['cols'] * specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
-          if lane_bytes == 16:
-            # input rows through the LDS ring: no prefetch registers (see
-            # kernel_stream2d_wp.emit); needs 16-byte lanes
-            options.setdefault('ring', AUTO_WP_RING)
-          # packable programs: one 512-column strip per wavefront, its two halves
-          # sharing register pairs (pairs=2; jacobi2d depth 16 per launch on
-          # 16384^2: 597 us against 627 us for two 256-column strips, pairs=1)
-          options.setdefault('pairs', 0 if not kernel_stream2d_wp.packable(spec)
-                             else 2 if options.get('ring') else 1)
-          if depth > PACKED_DEEP_DEPTH and options['pairs'] == 2:
-            # 5-6 levels per wavefront: three workgroups per CU (168 VGPRs;
-            # depth 24 left alone takes 174 = two per CU: 34.1 vs 33.2 us per
-            # iteration at 16384^2)
-            options.setdefault('waves_per_eu', PACKED_DEEP_WAVES_PER_EU)
-        try:
-          piped = kernel_stream2d_wp.emit(
-              spec, depth, groups=AUTO_WP_GROUPS if groups == -1 else groups,
-              **common, **options)
-          squeeze = (groups == -1 and options.get('ring') and
-                     'waves_per_eu' not in options and
-                     128 < piped[1]['est_vgprs'] <= AUTO_WP_SQUEEZE_VGPRS)
-          if squeeze and options.get('pairs') == 2 and options['ring'] == AUTO_WP_RING \
-              and 'max_period' not in options:
-            # a few registers over four workgroups per CU: cap them at 128.  In
-            # the wide form that pays only together with a 12-slot ring (10 rows
-            # in flight) unrolled over 12 rows: jacobi2d depth 16, 16384^2, per
-            # launch 578 us uncapped with ring 6, 830 us capped with ring 6,
-            # 560 us capped with ring 12.
-            piped = kernel_stream2d_wp.emit(
-                spec, depth, groups=AUTO_WP_GROUPS, waves_per_eu=4, **common,
-                **dict(options, ring=2 * AUTO_WP_RING, max_period=2 * AUTO_WP_RING))
-          elif squeeze and not options.get('pairs'):
-            # the scalar form: let the compiler spill the few registers over the cap
-            # (not the two-strip packed form: its scalar DPP adds then spill 45
-            # registers and lose 60 %)
-            piped = kernel_stream2d_wp.emit(
-                spec, depth, groups=AUTO_WP_GROUPS, waves_per_eu=4, **common,
-                **options)
-        except kernel_stream2d.NotFusable as e:
-          notes.append('depth %d not wave-pipelined: %s' % (depth, e))
-          if single is None and groups > 1:
-            try:
-              single = kernel_stream2d.emit(
-                  spec, depth, **common,
-                  **{k: v for k, v in fused_options.items()
-                     if k not in WP_ONLY_OPTIONS and k != 'nt'})
-            except kernel_stream2d.NotFusable as e2:
-              notes.append('depth %d not fused: %s' % (depth, e2))
-      if piped is None and single is None:
-        continue
-      ftext, entry = piped if piped is not None else single
-      parts.append(ftext)
-      table.append(annotate_cost(entry, spec))
-  if fused and spec['dim'] == 3:
-    wanted3 = [d for d in (1, 2) if d <= max(1, spec['iterate'])] \
-        if len(spec['inputs']) == len(spec['outputs']) == 1 else [1]
-    if depths is not None:
-      wanted3 = sorted(set([1] + list(depths))) if len(wanted3) > 1 else [1]
-    for depth in wanted3:
-      # rows per lane: as many as the register file allows (taller tiles waste
-      # less on the y halo)
-      options = {k: v for k, v in fused_options.items()
-                 if not k.startswith(('wp_', 'blk_')) and
-                 k not in ('deep3d', 'deep3d_from', 'nontemporal')}
-      # (rows, columns) per lane: the tallest tile the register file allows (taller
-      # tiles waste less on the y halo).  Programs with several live tensors
-      # (denoise3d, lowered to g and output over the inputs f and u) fit with one
-      # column per lane: 12 rows (156 VGPRs, three wavefronts per SIMD) before 16
-      # (235 VGPRs, two) - denoise3d per sweep at 256^3 / 512^3: 160 / 971 us against
-      # 200 / 999 us, the two per-stage launches 165 / 1281 us
-      narrow = [] if cols or len(spec['inputs']) == len(spec['outputs']) else \
-          [(12, 1), (16, 1)]      # (iteration chains go deep in the forms below)
-      shapes = [(options.pop('rows'), cols or 2)] if 'rows' in options else \
-          [(16, cols or 2), (12, cols or 2)] + narrow
-      error = None
-      options.setdefault('nt', 4)
-      for rows, lane_cols in shapes:
-        try:
-          ftext, entry = kernel_stream3d.emit(spec, depth, rows=rows, cols=lane_cols,
-                                              **options)
-        except kernel_stream2d.NotFusable as e:
-          error = e
-          continue
-        parts.append(ftext)
-        table.append(annotate_cost(entry, spec))
-        error = None
-        break
-      if error is not None:
-        notes.append('depth %d not fused: %s' % (depth, error))
-    # deeper than one wavefront's registers allow: one level per wavefront
-    # The block form serves the shallow depths as well (deep3d_from=3: not): next to the
-    # single-wave kernels above, which stay for arrays below its 128 x 64 tile and for
-    # programs it does not take.  jacobi3d per launch, depth 1 / 2: 512^3 470 / 395 us
-    # single-wave, 221 / 222 us block form (one read and one write of the array at 5.3
-    # TB/s: 203 us); 256^3 67 / 65 against 33 / 35; heat3d 512^3 depth 2 464 -> 231.
-    deep_from = fused_options.get('deep3d_from', 1)
-    deep = [d for d in sorted(set(depths if depths is not None else
-                                  BLOCK_3D_SHALLOW_DEPTHS + DEEP_3D_DEPTHS))
-            if d >= deep_from and d <= max(1, spec['iterate'])]
-    if len(spec['inputs']) == len(spec['outputs']) == 1 and (
-        depths is not None or arithmetic_weight(spec) <= DEEP_3D_MAX_WEIGHT):
-      for depth in deep:
-        form = fused_options.get('deep3d', DEEP_3D_FORM)
-        if depth < 3 and form == 'wp':      # one level per wavefront needs >= 3 levels
-          continue
-        if form in ('blk', 'both'):
-          # block form: all levels in every wavefront, edge rows through LDS
-          # (kernel_stream3d_blk).  Named <app>_fused_k<d>b; with 'both' it ships
-          # NEXT TO the wave-pipelined kernel and the run-time picks per launch
-          given = prefixed_options(fused_options, 'blk_', kernel_stream3d_blk.emit)
-          heavy = arithmetic_weight(spec) > PACKED_3D_LIGHT_WEIGHT
-          ring_forms = [dict(BLOCK_3D_RING_OPTIONS)]
-          if heavy and kernel_stream2d_wp.packable(spec):
-            # heavy plain-float programs: packed pair-rows first (heat3d 512^3 x20,
-            # block form alone, clocks warm: 1.76 ms plain, 1.42 packed - 13.2 k instead
-            # of 22.6 k VALU instructions per unrolled loop, 254 VGPRs without spills
-            # now that the ring took the prefetch registers; a hand-ordered scalar
-            # instruction stream, round 3's kernel_asm, reached 1.49 and is gone)
-            # (and exact store ranges: whole 64-byte pieces cost this kernel 3 %,
-            # heat3d 512^3 x20 1.37 -> 1.41 ms, where they gain jacobi3d's 2 %)
-            ring_forms.insert(0, dict(BLOCK_3D_RING_OPTIONS, pairs=1, wide_stores=0))
-          attempts = [BLOCK_3D_OPTIONS] if 'prefetch' in given or 'ring' in given else \
-              ring_forms + [BLOCK_3D_OPTIONS]
-          try:
-            for k, base in enumerate(attempts):
-              options = dict(base)
-              options.update(given)
-              try:
-                ftext, entry = kernel_stream3d_blk.emit(spec, depth, **options)
-                break
-              except kernel_stream2d.NotFusable:
-                if k == len(attempts) - 1:
-                  raise
-            parts.append(ftext)
-            table.append(annotate_cost(entry, spec))
-            if form == 'blk' or depth < 3:
-              continue
-          except kernel_stream2d.NotFusable as e:
-            notes.append('depth %d not in block form: %s' % (depth, e))
-            if depth < 3:
-              continue
-        options = prefixed_options(fused_options, 'wp_', kernel_stream3d_wp.emit)
-        options.setdefault('groups', min(depth * len(spec['stages']), 4))
-        # (no non-temporal stores here: heat3d 512^3 x20 with this form alone 2.09 ms
-        # without, 2.12 ms with wp_nt=4)
-        if options.get('split', 2) == 2 and not options.get('loader') and \
-            options.get('rows', 16) % 2 == 0 and kernel_stream2d_wp.packable(spec):
-          # packed pair-rows (v_pk_*_f32) for programs heavy enough on arithmetic:
-          # heat3d (weight 15) 459 us per launch scalar, 383-440 us packed at the
-          # 230 VGPRs the compiler asks for (629 us capped at three workgroups per
-          # CU: 360 spilled registers).  Light programs are bounded by memory and
-          # keep the scalar form at three workgroups per CU: jacobi3d (weight 7),
-          # cfg5 with the offline compiler: 6.23 ms scalar, 7.43 ms packed (36
-          # spilled registers); hiprtc happens to favour the packed form (6.31 vs
-          # 6.63 ms) - the shipped code objects are built by hipcc.
-          options.setdefault('pairs', int(arithmetic_weight(spec) >
-                                          PACKED_3D_LIGHT_WEIGHT))
-          if options['pairs']:
-            options.setdefault('waves_per_eu', 0)
-        try:
-          ftext, entry = kernel_stream3d_wp.emit(spec, depth, **options)
-        except kernel_stream2d.NotFusable as e:
-          notes.append('depth %d not wave-pipelined: %s' % (depth, e))
-          continue
-        parts.append(ftext)
-        table.append(annotate_cost(entry, spec))
   if notes:
     parts.append(''.join('// %s\n' % n for n in notes))
   parts.append(kernel_common.meta_symbol(

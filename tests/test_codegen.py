@@ -694,3 +694,85 @@ def test_edge_tiles_cover_every_box_exactly_once():
   slack = {k['name']: k.get('edge_slack', 0) for k in kernel.generate(spec)[1]}
   assert slack['jacobi3d_fused_k4b'] == 8 and slack['jacobi3d_fused_k1b'] == 12
   assert slack['jacobi3d_fused_k4'] == 0
+
+
+def test_first_fusable_returns_the_first_success_or_the_last_error():
+  """The try-next helper of the kernel selection: the first attempt that does not raise
+  NotFusable wins and later ones are not made; when all raise, no result and the LAST
+  error (the one the generated text's note quotes)."""
+  calls = []
+
+  def emit(spec, depth, tag, fuses):
+    calls.append(tag)
+    if not fuses:
+      raise kernel_stream2d.NotFusable('no %s at depth %d' % (tag, depth))
+    return 'text of ' + tag, dict(name=tag, spec=spec)
+
+  attempts = [(emit, dict(tag='a', fuses=False)), (emit, dict(tag='b', fuses=True)),
+              (emit, dict(tag='c', fuses=True))]
+  found, error = kernel.first_fusable('spec', 3, attempts)
+  assert found == ('text of b', dict(name='b', spec='spec')) and error is None
+  assert calls == ['a', 'b']
+  found, error = kernel.first_fusable('spec', 3, [(emit, dict(tag=t, fuses=False))
+                                                  for t in 'xyz'])
+  assert found is None and isinstance(error, kernel_stream2d.NotFusable)
+  assert str(error) == 'no z at depth 3'
+  assert kernel.first_fusable('spec', 3, []) == (None, None)
+  with pytest.raises(TypeError):      # only NotFusable means "try the next"
+    kernel.first_fusable('spec', 3, [(emit, dict(tag='a')), (emit, dict(tag='b', fuses=True))])
+
+
+# generate() options on one program of each kernel family - multi-field 2-D, single-array
+# 2-D, 3-D chain (shallow and deep forms), 3-D without a chain: True where the call succeeds
+# (the option is used, or silently not passed to a form that does not take it), False where
+# it is a TypeError.  Every outcome is what the generator did before its selection was split
+# into one function per family (recorded by running these calls on that commit); tools pass
+# one option set across programs of all families and rely on it.
+ROUTING_APPS = (('jacobi2d', 8), ('wave2d', 8), ('jacobi3d', 8), ('denoise3d', None))
+OPTION_ROUTING = [
+    (dict(sync=3), (False, True, False, False)),
+    (dict(depths=[8], wave_groups=4, sync=3), (False, True, False, False)),
+    (dict(blk_skip_fill=1), (False, True, False, True)),
+    (dict(blk_asm_sched=1), (False, True, False, True)),
+    (dict(wp_pairs=1), (False, True, True, True)),
+    (dict(blk_pairs=0), (False, True, True, True)),
+    (dict(wp_bogus=1), (False, True, False, True)),
+    (dict(deep3d='wp', blk_bogus=1), (False, True, True, True)),
+    (dict(nt=2), (True, True, True, True)),
+    (dict(nontemporal=0), (True, True, True, True)),
+    (dict(deep3d='blk'), (False, True, True, True)),
+    (dict(deep3d_from=3), (False, True, True, True)),
+    (dict(pairs=1), (True, True, False, False)),
+    (dict(vgpr_budget=120), (True, True, True, True)),
+    (dict(skip_fill=0), (True, True, False, False)),
+    (dict(rows=8), (False, True, True, True)),
+    (dict(align='full'), (True, True, False, False)),
+    (dict(bogus=1), (False, True, False, False)),
+]
+
+
+@pytest.mark.parametrize('column', range(len(ROUTING_APPS)), ids=[a for a, _ in ROUTING_APPS])
+def test_option_routing_per_family(column):
+  app, iterate = ROUTING_APPS[column]
+  path = os.path.join(SAMPLES, app + '.soda')
+  path = path if os.path.exists(path) else os.path.join(SAMPLES, 'extra', app + '.soda')
+  spec = specmod.spec_from_stencil(frontend.load(path, iterate=iterate))
+  for options, accepted in OPTION_ROUTING:
+    if accepted[column]:
+      text, table = kernel.generate(spec, **options)
+      assert 'soda_hip_meta' in text and table, (app, options)
+    else:
+      with pytest.raises(TypeError):
+        kernel.generate(spec, **options)
+
+
+def test_kernel_families_enter_the_table_in_order():
+  """Stage kernels, then per family: the single-wave 3-D kernels, then per depth the block
+  form and the wave-pipelined kernel.  The run time reads the table in this order; a
+  reordering of generate()'s loop over the families shows here."""
+  names = [k['name'] for k in kernel.generate(spec_of('jacobi3d', iterate=8))[1]]
+  assert names == ['jacobi3d_stage_t0'] + ['jacobi3d_fused_' + k
+                                           for k in ('k1', 'k2', 'k1b', 'k2b', 'k4b', 'k4')]
+  # 2-D: one family per program (multi-field or single-array), depths ascending
+  names = [k['name'] for k in kernel.generate(spec_of('jacobi2d', iterate=16))[1]]
+  assert names == ['jacobi2d_stage_t0'] + ['jacobi2d_fused_k%d' % d for d in (1, 2, 4, 8, 12, 16)]
