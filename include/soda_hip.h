@@ -256,7 +256,16 @@ typedef struct soda_hip_args {
                        That is room for 6 outputs; programs with more keep their
                        per-stage kernels.  The grid covers the union of the boxes
                        (the box widened by the largest extra per side).  All zero
-                       = every output on [box_lo, box_hi). */
+                       = every output on [box_lo, box_hi).
+                       Fused 3-D kernels of such programs (they use none of the
+                       xcd_tiles placements): the same with six extras per output
+                       and one word per output, output j in param[1 + j]:
+                         lo0 | lo1 << 8 | lo2 << 16 | hi0 << 24 | hi1 << 32 |
+                         hi2 << 40,
+                       each 0..255: output j is stored on
+                         [box_lo[d] - lo_d, box_hi[d] + hi_d), d = 0, 1, 2.
+                       That is room for 3 outputs; programs with more keep their
+                       per-stage kernels. */
 } soda_hip_args;
 
 /* ---- plan -------------------------------------------------------------------

@@ -199,33 +199,38 @@ std::array<int64_t, 5> split_key(const Planner* plan, const int64_t* dims, int i
 
 namespace {
 
-// Fused 2-D kernels of programs with several outputs (kernel_fields2d.py) store output j
-// on a box of its own: the launch's box - the intersection of the outputs' boxes -
-// widened by the four extras of soda_hip_args.param[1..3] (include/soda_hip.h).
-constexpr int kMaxExtraOutputs = 6;     // 3 words x 64 bits / (4 x 8 bits per output)
+// Fused kernels of programs with several outputs (kernel_fields2d.py, kernel_fields3d.py)
+// store output j on a box of its own: the launch's box - the intersection of the outputs'
+// boxes - widened by the extras of soda_hip_args.param[1..3] (include/soda_hip.h): 2-D four
+// extras of 8 bits per output, two outputs to a word; 3-D six, one output to a word.
 constexpr int kMaxExtra = 255;
 
+int max_extra_outputs(int dim) { return dim == 2 ? 6 : 3; }
+
 bool takes_output_extras(const Planner* plan, const soda_hip_kernel& desc) {
-  return desc.kind == SODA_HIP_KERNEL_FUSED && plan->prog.dim == 2 && plan->prog.n_outputs > 1;
+  return desc.kind == SODA_HIP_KERNEL_FUSED && (plan->prog.dim == 2 || plan->prog.dim == 3) &&
+         plan->prog.n_outputs > 1;
 }
 
-// extras of output j: {lo x, lo y, hi x, hi y}
-void unpack_extras(const soda_hip_args& a, int j, int64_t* ex) {
-  const uint64_t word = (uint64_t)a.param[1 + j / 2] >> (32 * (j % 2));
-  for (int i = 0; i < 4; ++i) ex[i] = (word >> (8 * i)) & 0xff;
+// extras of output j: {lo of dimension 0 .. dim - 1, hi of dimension 0 .. dim - 1}
+void unpack_extras(int dim, const soda_hip_args& a, int j, int64_t* ex) {
+  const uint64_t word = dim == 2 ? (uint64_t)a.param[1 + j / 2] >> (32 * (j % 2))
+                                 : (uint64_t)a.param[1 + j];
+  for (int i = 0; i < 2 * dim; ++i) ex[i] = (word >> (8 * i)) & 0xff;
 }
 
-// the union of the outputs' boxes: what the strips and chunks of such a launch cover
+// the union of the outputs' boxes: what the tiles and chunks of such a launch cover
 void widen_to_union(const Planner* plan, soda_hip_args* a) {
-  int64_t most[4] = {0, 0, 0, 0};
+  const int dim = plan->prog.dim;
+  int64_t most[6] = {0, 0, 0, 0, 0, 0};
   for (int j = 0; j < plan->prog.n_outputs; ++j) {
-    int64_t ex[4];
-    unpack_extras(*a, j, ex);
-    for (int i = 0; i < 4; ++i) most[i] = std::max(most[i], ex[i]);
+    int64_t ex[6];
+    unpack_extras(dim, *a, j, ex);
+    for (int i = 0; i < 2 * dim; ++i) most[i] = std::max(most[i], ex[i]);
   }
-  for (int d = 0; d < 2; ++d) {
+  for (int d = 0; d < dim; ++d) {
     a->box_lo[d] -= most[d];
-    a->box_hi[d] += most[2 + d];
+    a->box_hi[d] += most[dim + d];
   }
 }
 
@@ -563,7 +568,7 @@ bool plans_fused(const Planner* plan, const std::vector<int>& fused, const int64
   if (plan->max_depth == 0 && !plan->tuning &&
       takes_output_extras(plan, plan->kernels[fused.back()])) {
     // The fused kernels over several fields have not been timed on an MI355X yet
-    // (profiles/r07_fields.txt), so no depth of theirs has earned its place in the default
+    // (profiles/r07_fields.txt, r07_fields3d.txt), so no depth of theirs has earned its place in the default
     // schedule: they run where the caller asks for them, with a depth limit
     // (soda_hip_plan_set_max_depth > 0) or a split (soda_hip_plan_set_split, _tune).
     return plan->tuned_split.find(split_key(plan, dims, iterate)) != plan->tuned_split.end();
@@ -706,29 +711,32 @@ std::vector<Buffer> sweep_inputs(const Planner* plan) {
 int pack_output_extras(const Planner* plan, const soda_hip_kernel& desc, int level,
                        const int32_t* mlo, const int32_t* mhi, soda_hip_args* a) {
   const soda_hip_program& p = plan->prog;
-  if (p.n_outputs > kMaxExtraOutputs)
+  const int dim = p.dim;
+  if (p.n_outputs > max_extra_outputs(dim))
     return fail(SODA_HIP_ERR_INTERNAL, "kernel %s: %d outputs, the launch arguments "
-                "carry the boxes of %d", desc.name, p.n_outputs, kMaxExtraOutputs);
+                "carry the boxes of %d", desc.name, p.n_outputs, max_extra_outputs(dim));
   const std::vector<Box>& boxes = plan->boxes[level - 1];
   for (int j = 0; j < p.n_outputs; ++j) {
     const Box& o = boxes[p.output_tensor[j]];
-    const int64_t ex[4] = {mlo[0] + o.lo[0], mlo[1] + o.lo[1], mhi[0] - o.hi[0],
-                           mhi[1] - o.hi[1]};
+    int64_t ex[6];
     soda_hip_args own = *a;      // the widened box must lie inside the array as well
-    for (int d = 0; d < 2; ++d) {
-      if (ex[d] < 0 || ex[d] > kMaxExtra || ex[2 + d] < 0 || ex[2 + d] > kMaxExtra)
+    for (int d = 0; d < dim; ++d) {
+      ex[d] = mlo[d] + o.lo[d];
+      ex[dim + d] = mhi[d] - o.hi[d];
+      if (ex[d] < 0 || ex[d] > kMaxExtra || ex[dim + d] < 0 || ex[dim + d] > kMaxExtra)
         return fail(SODA_HIP_ERR_INTERNAL, "kernel %s: output %d is %lld / %lld cells "
                     "wider than the launch's box in dimension %d (limit %d)", desc.name,
-                    j, (long long)ex[d], (long long)ex[2 + d], d, kMaxExtra);
+                    j, (long long)ex[d], (long long)ex[dim + d], d, kMaxExtra);
       own.box_lo[d] -= ex[d];
-      own.box_hi[d] += ex[2 + d];
+      own.box_hi[d] += ex[dim + d];
     }
     const int32_t none[SODA_HIP_MAX_DIMS] = {0, 0, 0, 0};
     int rc = check_box_inside(plan, own, none, none);
     if (rc) return rc;
-    const uint64_t word = (uint64_t)ex[0] | (uint64_t)ex[1] << 8 |
-                          (uint64_t)ex[2] << 16 | (uint64_t)ex[3] << 24;
-    a->param[1 + j / 2] |= (int64_t)(word << (32 * (j % 2)));
+    uint64_t word = 0;
+    for (int i = 0; i < 2 * dim; ++i) word |= (uint64_t)ex[i] << (8 * i);
+    if (dim == 2) a->param[1 + j / 2] |= (int64_t)(word << (32 * (j % 2)));
+    else a->param[1 + j] = (int64_t)word;
   }
   return 0;
 }

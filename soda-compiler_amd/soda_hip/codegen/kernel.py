@@ -10,6 +10,7 @@ The unit holds
   * one per-stage kernel per stage (kernel_stage.py), always;
   * the fused kernels of the program's family, at the depths selected below:
       multi-field 2-D   kernel_fields2d
+      multi-field 3-D   kernel_fields3d
       single-array 2-D  kernel_stream2d (one strip per wavefront) or, deep,
                         kernel_stream2d_wp (wave-pipelined)
       3-D, depth 1-2    kernel_stream3d (one tile per wavefront)
@@ -30,7 +31,7 @@ import subprocess
 import tempfile
 
 from .. import __version__
-from . import (kernel_common, kernel_fields2d, kernel_stage, kernel_stream2d,
+from . import (kernel_common, kernel_fields2d, kernel_fields3d, kernel_stage, kernel_stream2d,
                kernel_stream2d_wp, kernel_stream3d, kernel_stream3d_blk, kernel_stream3d_wp)
 from . import spec as specmod
 
@@ -125,6 +126,11 @@ ALIGN_FULL_MAX_WEIGHT = 40
 # depths of the multi-field form (kernel_fields2d)
 FIELDS_DEPTHS = (1, 2, 4, 8)
 FIELDS_OPTIONS = ('skip_fill', 'vgpr_budget', 'max_period', 'waves_per_eu')
+# ... and of its 3-D counterpart (kernel_fields3d): with the planes of every field of every
+# iteration in one wavefront's registers, depth 2 is as deep as two- and three-field
+# programs go in tiles that keep any cells
+FIELDS3D_DEPTHS = (1, 2)
+FIELDS3D_OPTIONS = ('rows', 'vgpr_budget', 'max_period', 'waves_per_eu')
 
 # generator options of the fused 2-D forms that `generate` passes through:
 # those both forms understand, and those only the wave-pipelined form has
@@ -366,12 +372,13 @@ def prefixed_options(options, prefix, emit):
 # Which of generate()'s `**fused_options` a kernel form receives: the one place that says so.
 # Tools pass one option set across programs of different families, so what a form does not
 # receive is dropped in silence, while a name that reaches an emit() which does not take it
-# is a TypeError.  fields2d and stream2d_wp receive the names listed for them; stream2d and
+# is a TypeError.  fields2d, fields3d and stream2d_wp receive the names listed for them; stream2d and
 # stream3d every name but those held back for the other forms (a name nobody knows therefore
 # ends in their emit()); stream3d_blk and stream3d_wp the `blk_` / `wp_` names, checked
 # against the emit() by prefixed_options.
 FORM_OPTIONS = dict(
     fields2d=lambda k: k in FIELDS_OPTIONS,
+    fields3d=lambda k: k in FIELDS3D_OPTIONS,
     stream2d=lambda k: k not in WP_ONLY_OPTIONS and k != 'nt',
     stream2d_wp=lambda k: k in SHARED_2D_OPTIONS + WP_ONLY_OPTIONS,
     stream3d=lambda k: not k.startswith(('wp_', 'blk_')) and
@@ -412,7 +419,9 @@ class Request:
                       prefetch=3 if prefetch is None else prefetch)
     self.groups = WAVE_GROUPS if wave_groups is None else wave_groups
     self.single_array = len(spec['inputs']) == len(spec['outputs']) == 1
-    if spec['dim'] == 3:
+    if spec['dim'] == 3 and kernel_stream2d.multi_field(spec):
+      self.default_depths = [d for d in FIELDS3D_DEPTHS if d <= max(1, spec['iterate'])]
+    elif spec['dim'] == 3:
       self.default_depths = [d for d in (1, 2) if d <= max(1, spec['iterate'])] \
           if self.single_array else [1]
     else:
@@ -433,6 +442,32 @@ def fields2d_kernels(req, notes):
   for depth in wanted:
     found, error = first_fusable(spec, depth, [
         (kernel_fields2d.emit, dict(req.strip, **form_options('fields2d', req.options)))])
+    if found is None:
+      notes.append('depth %d not fused: %s' % (depth, error))
+      if depth == 1:      # the scheduler needs depth 1: without it, per-stage kernels
+        return
+      continue
+    yield found
+
+
+def fields3d_kernels(req, notes):
+  """Multi-field 3-D programs: kernel_fields3d at each depth, in the tile shape that keeps
+  most of the tile among those the register budget takes."""
+  spec = req.spec
+  if spec['dim'] != 3 or not kernel_stream2d.multi_field(spec):
+    return
+  wanted = req.default_depths
+  if req.depths is not None:
+    wanted = sorted(set([1] + list(req.depths)))
+  for depth in wanted:
+    options = form_options('fields3d', req.options)
+    shapes = [s for s in kernel_fields3d.shapes_by_kept_fraction(spec, depth)
+              if not req.cols or s[1] == req.cols]
+    if 'rows' in options:
+      shapes = [(options.pop('rows'), req.cols or 2)]
+    found, error = first_fusable(spec, depth, [
+        (kernel_fields3d.emit, dict(options, rows=rows, cols=lane_cols))
+        for rows, lane_cols in shapes])
     if found is None:
       notes.append('depth %d not fused: %s' % (depth, error))
       if depth == 1:      # the scheduler needs depth 1: without it, per-stage kernels
@@ -581,7 +616,7 @@ def stream2d_kernels(req, notes):
 def stream3d_kernels(req, notes):
   """3-D programs, depths 1 and 2: one tile per wavefront (kernel_stream3d)."""
   spec, cols = req.spec, req.cols
-  if spec['dim'] != 3:
+  if spec['dim'] != 3 or kernel_stream2d.multi_field(spec):
     return
   wanted = req.default_depths
   if req.depths is not None:
@@ -699,7 +734,8 @@ def deep3d_kernels(req, notes):
 
 # the kernel families in the order their kernels enter the table; each yields the
 # (text, entry) of the kernels it selects for this request and appends to `notes`
-FAMILIES = (fields2d_kernels, stream2d_kernels, stream3d_kernels, deep3d_kernels)
+FAMILIES = (fields2d_kernels, fields3d_kernels, stream2d_kernels, stream3d_kernels,
+            deep3d_kernels)
 
 
 def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,

@@ -31,13 +31,14 @@ def kernel_name(spec, depth):
   return '%s_fused_k%d' % (spec['app_name'], depth)
 
 
-def pipeline(spec, depth, prefetch):
+def pipeline(spec, depth, prefetch, fields=False):
   """build_pipeline() streams along dimension 1; re-key the loads so that it
-  sees the plane offset there, then restore the full offsets."""
+  sees the plane offset there, then restore the full offsets.  fields: as in
+  build_pipeline (kernel_fields3d)."""
   flat = dict(spec, dim=2)
   flat['stages'] = [dict(s, loads=[[t, [rel[0], rel[2]]] for t, rel in s['loads']])
                     for s in spec['stages']]
-  insts, final = build_pipeline(flat, depth, prefetch)
+  insts, final = build_pipeline(flat, depth, prefetch, fields=fields)
   # build_pipeline de-duplicated nothing (loads are unique in 3-D already, but
   # two 3-D loads can collapse onto one (x, z) pair): rebuild reads in 3-D
   by_ident = {i.ident: i for i in insts}

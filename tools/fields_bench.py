@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """Multi-field programs, fused against per-stage, on one GPU: wave2d and fdtd2d at
-8192 x 8192 x 100 iterations under bench.py's protocol (warm-up sweeps, then the median
+8192 x 8192 x 100 iterations or, with `--apps 3d` (wave3d and maxwell3d), at
+384 x 384 x 384 x 20, under bench.py's protocol (warm-up sweeps, then the median
 of event-timed sweeps; sweeps are repeated until the timed region is long enough for
 steady clocks).
 
 Per program: the scheduler's own split of the fused depths (set_max_depth(8); without a
 limit these programs run per stage until this measurement admits a depth), the per-stage
 schedule, and every fused depth of
-the table alone (the sweep as 100 / d launches of depth d), alternating so that clock
+the table alone (the sweep as N / d launches of depth d), alternating so that clock
 drift hits all of them alike.  The per-stage schedule is set_max_depth(-1): one launch
 per stage per iteration, every field through HBM every iteration.  It stands for the
 commit before the fused multi-field kernels, which had nothing else for these programs:
@@ -17,10 +18,12 @@ device, interleaved.
 
 A depth SHIPS if its median time per iteration is below the per-stage one by more than
 the run-to-run spread: the larger of the two schedules' (max - min) over the timed sweeps.
-Registers, occupancy and scratch per kernel are read from the code object's metadata.
+Registers, occupancy and scratch per kernel are read from the code object's metadata; for
+the 3-D kernels the tile and the fraction of it that survives the halo come from the table.
 Prints one JSON line per program and writes the whole table to the file given with --out.
 
-    python tools/fields_bench.py [--size W H] [--iterate N] [--sweeps K] [--out FILE]
+    python tools/fields_bench.py [--apps 2d | 3d | APP ...] [--size W H [D]] [--iterate N]
+                                 [--sweeps K] [--out FILE]
 """
 import argparse
 import json
@@ -37,6 +40,7 @@ for p in (ROOT, os.path.join(ROOT, 'soda-compiler_amd'), os.path.join(ROOT, 'tes
 
 
 READELF = '/opt/rocm/lib/llvm/bin/llvm-readelf'
+DEFAULTS = {'2d': ('wave2d', 'fdtd2d'), '3d': ('wave3d', 'maxwell3d')}
 
 
 def isa_figures(blob, names):
@@ -58,9 +62,12 @@ def isa_figures(blob, names):
 def main():
   ap = argparse.ArgumentParser(description=__doc__,
                                formatter_class=argparse.RawDescriptionHelpFormatter)
-  ap.add_argument('--apps', nargs='+', default=['wave2d', 'fdtd2d'])
-  ap.add_argument('--size', nargs=2, type=int, default=[8192, 8192])
-  ap.add_argument('--iterate', type=int, default=100)
+  ap.add_argument('--apps', nargs='+', default=['2d'],
+                  help="'2d' = wave2d fdtd2d, '3d' = wave3d maxwell3d, or sample names of "
+                  'one dimensionality')
+  ap.add_argument('--size', nargs='+', type=int, default=None,
+                  help='default 8192 8192, for 3-D programs 384 384 384')
+  ap.add_argument('--iterate', type=int, default=None, help='default 100, for 3-D programs 20')
   ap.add_argument('--sweeps', type=int, default=7, help='timed sweeps per schedule (>= 3)')
   ap.add_argument('--warmup', type=int, default=3)
   ap.add_argument('--out', default=None)
@@ -71,6 +78,11 @@ def main():
   from soda_hip.codegen import spec as specmod
   from soda_hip.runtime import host
   assert args.sweeps >= 3
+  args.apps = [a for name in args.apps for a in DEFAULTS.get(name, (name,))]
+  dim = specmod.spec_from_stencil(frontend.load(entry.sample_path(args.apps[0])))['dim']
+  args.size = args.size or ([8192, 8192] if dim == 2 else [384, 384, 384])
+  args.iterate = args.iterate or (100 if dim == 2 else 20)
+  assert len(args.size) == dim, '--size needs %d extents' % dim
   dims = tuple(args.size)
   shape = tuple(reversed(dims))
   compiler = ''
@@ -81,7 +93,8 @@ def main():
   except (OSError, subprocess.CalledProcessError):
     pass
   lines = [
-      'Multi-field fused 2-D kernels (codegen/kernel_fields2d.py) against the per-stage schedule',
+      'Multi-field fused %d-D kernels (codegen/kernel_fields%dd.py) against the per-stage schedule'
+      % (dim, dim),
       'tools/fields_bench.py: warm-up, then the median of event-timed sweeps, schedules interleaved.',
       'per-stage = set_max_depth(-1): it stands for the commit before these kernels, whose stage',
       'kernels have byte for byte this text and which had nothing else for these programs.',
@@ -90,6 +103,7 @@ def main():
       % (compiler or '(unknown)'), '']
   for app in args.apps:
     spec = specmod.spec_from_stencil(frontend.load(entry.sample_path(app)))
+    assert spec['dim'] == dim, '%s is not a %d-D program' % (app, dim)
     blob = entry.blob_path(app)
     prog = host.open_program(blob=blob, spec=spec)
     rng = np.random.default_rng(7)
@@ -134,8 +148,8 @@ def main():
     alg = specmod.algorithmic_bytes_per_update(spec)
     result = dict(app=app, dims=list(dims), iterate=args.iterate, sweeps=args.sweeps,
                   algorithmic_bytes_per_update=alg, schedules={})
-    lines.append('%s %d x %d x %d, %d timed sweeps each (ms per sweep: median, min .. max)'
-                 % (app, dims[0], dims[1], args.iterate, args.sweeps))
+    lines.append('%s %s x %d, %d timed sweeps each (ms per sweep: median, min .. max)'
+                 % (app, ' x '.join(map(str, dims)), args.iterate, args.sweeps))
     stage = sorted(times['per-stage'])
     stage_med, stage_range = statistics.median(stage), stage[-1] - stage[0]
     for name, limit, split in schedules:
@@ -166,6 +180,11 @@ def main():
                        kname, f['vgpr_count'], min(8, 512 // (-(-f['vgpr_count'] // 8) * 8)),
                        f['sgpr_count'], f['private_segment_fixed_size'],
                        f['vgpr_spill_count'], f['sgpr_spill_count']))
+    for k in sorted((k for k in prog.kernels if k['kind'] == 'fused' and 'rows' in k),
+                    key=lambda k: k['depth']):
+      lines.append('  %-22s tile %d x %d per wavefront, %d x %d stored: %.2f of it kept' % (
+          k['name'], 64 * k['cols'], k['rows'], k['w_out'], k['r_out'],
+          k['w_out'] * k['r_out'] / (64.0 * k['cols'] * k['rows'])))
     lines.append('  algorithmic bytes per cell-update: %d (per-stage moves more: every stage '
                  'reads its operands from and writes its result to HBM)' % alg)
     print(json.dumps(result))
