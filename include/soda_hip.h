@@ -289,6 +289,15 @@ int soda_hip_plan_margins(const soda_hip_plan* plan, int iterations,
                           int32_t lo[SODA_HIP_MAX_DIMS],
                           int32_t hi[SODA_HIP_MAX_DIMS]);
 
+/* The same per output: output j of a fresh run of `iterations` iterations is defined on
+ * [lo[j][d], dims[d] - hi[j][d]); n_outputs rows each.  soda_hip_plan_margins returns the
+ * hull of these (the largest margin per side).  What a caller that resumes a program over
+ * several fields passes to soda_hip_sweep_fields as the valid regions of its inputs
+ * (output j feeds input j). */
+int soda_hip_plan_field_margins(const soda_hip_plan* plan, int iterations,
+                                int32_t (*lo)[SODA_HIP_MAX_DIMS],
+                                int32_t (*hi)[SODA_HIP_MAX_DIMS]);
+
 typedef struct soda_hip_timing {
   double kernel_us;     /* device time of the timed sweep loop (hipEvents) */
   int32_t launches;     /* kernel launches in one sweep loop */
@@ -330,6 +339,27 @@ int soda_hip_sweep(soda_hip_plan* plan, void* const* in, void* const* out,
                    const int32_t* valid_lo, const int32_t* valid_hi,
                    void* stream);
 
+/* soda_hip_sweep with a valid region PER INPUT: valid_lo / valid_hi hold n_inputs rows of
+ * SODA_HIP_MAX_DIMS margins, input j being defined on [valid_lo[j][d], dims[d] -
+ * valid_hi[j][d]); NULL means the whole array.  In a program over several fields every
+ * field lives on a box of its own after t iterations (soda_hip_plan_field_margins), and a
+ * resumed sweep has to be told each of them to end on the boxes of one uninterrupted run.
+ * Contract: after the call output j is defined on the box the composition of the read
+ * windows (iteration_boxes of soda_hip/codegen/spec.py) gives had the inputs been defined
+ * on their regions - t1 iterations, then t2 more from soda_hip_plan_field_margins(t1),
+ * define exactly the boxes of t1 + t2 iterations in one call.  The margins ALL inputs
+ * share only move the boxes (no output is defined outside them: one margin repeated for
+ * every input is soda_hip_sweep with that margin, which is how soda_hip_sweep is
+ * implemented); what a region lacks beyond them is composed through the windows.  A
+ * fused kernel's launch arguments carry at most 255 cells between an output's box and
+ * the launch's (soda_hip_args.param): regions that differ by more are
+ * SODA_HIP_ERR_INTERNAL under the fused kernels, never a wrong box.  The memory contract
+ * is soda_hip_sweep's. */
+int soda_hip_sweep_fields(soda_hip_plan* plan, void* const* in, void* const* out,
+                          const int64_t dims[SODA_HIP_MAX_DIMS], int iterate,
+                          const int32_t (*valid_lo)[SODA_HIP_MAX_DIMS],
+                          const int32_t (*valid_hi)[SODA_HIP_MAX_DIMS], void* stream);
+
 /* Same, bracketed by hipEvents on `stream`: `warmup` untimed runs, then
  * `repeats` timed ones (reference protocol host.py:775-796: one warm-up, one
  * timed run).  Synchronises the stream. */
@@ -349,6 +379,16 @@ int soda_hip_plan_schedule(soda_hip_plan* plan,
                            const int32_t* valid_lo, const int32_t* valid_hi,
                            int32_t* kernel_index, double* est_us, int capacity,
                            int* n_launches);
+
+/* The launch list of soda_hip_sweep_fields; args[i] (may be NULL) additionally receives
+ * the launch's arguments - its box and, for the fused kernels over several outputs, the
+ * extras of every output's own box in param[1..3] - with every tensor pointer NULL. */
+int soda_hip_plan_schedule_fields(soda_hip_plan* plan,
+                                  const int64_t dims[SODA_HIP_MAX_DIMS], int iterate,
+                                  const int32_t (*valid_lo)[SODA_HIP_MAX_DIMS],
+                                  const int32_t (*valid_hi)[SODA_HIP_MAX_DIMS],
+                                  int32_t* kernel_index, double* est_us,
+                                  soda_hip_args* args, int capacity, int* n_launches);
 
 /* Restricts fused kernels to depth <= max_depth (0 = no limit, < 0 = per-stage
  * kernels only); for tests and tuning.  The fused kernels of programs with several
@@ -540,6 +580,28 @@ int soda_hip_slab_layout(const soda_hip_plan* plan, const soda_hip_slab* slab, i
 int soda_hip_run_slab(soda_hip_plan* plan, const soda_hip_slab* slab, void* comm,
                       void* a, void* b, void* c, int iterate, void* stream,
                       void** result, int* exchanges);
+
+/* soda_hip_run_slab for a program over several fields (as many outputs as inputs, output j
+ * feeding input j: wave2d, fdtd2d, maxwell3d ...): a[j], b[j], c[j] are field j's three
+ * arrays, result[j] receives b[j] or c[j].  The slab's geometry is the same for every
+ * field and is what soda_hip_slab_layout / soda_hip_slab_extent describe: reach_lo /
+ * reach_hi are the hull over the fields, soda_hip_plan_margins(plan, 1) - the composed
+ * margin of any field after k iterations is at most k times that hull, so `exchange x
+ * reach` ghost rows suffice for every field (a smaller reach is refused).  Per super-step
+ * ONE group carries every field's ghost rows - the rows of one field are contiguous, so
+ * nothing is packed: one send and one receive per field and neighbour, field by field -
+ * then the slab advances with soda_hip_sweep_fields: the ghost sides fully valid for every
+ * field, the global sides OF EVERY DIMENSION carrying each field's own margin after the
+ * iterations done so far (soda_hip_plan_field_margins), so every rank's own rows of field
+ * j end on exactly the cells of j's box of an undivided run.
+ * Static cut and serial order only: SODA_HIP_SLAB_CUT_RECUT and SODA_HIP_SLAB_BANDS_FIRST
+ * are SODA_HIP_ERR_CONSTRAINT here, found - like every other fault of the call itself -
+ * before the first message.  The failure contract is soda_hip_run_slab's.  Tested as
+ * soda_hip_run_slab is: world == 1, and worlds 2 to 4 over the test-only stand-in; no real
+ * RCCL with more than one rank has run it. */
+int soda_hip_run_slab_fields(soda_hip_plan* plan, const soda_hip_slab* slab, void* comm,
+                             void* const* a, void* const* b, void* const* c, int iterate,
+                             void* stream, void** result, int* exchanges);
 
 /* ---- host-buffer entry (the generated `<app>`) ------------------------------
  * Legacy Halide buffer_t, bit-compatible with the struct the reference's

@@ -38,19 +38,22 @@ bool is_output_tensor(const soda_hip_program& p, int t) {
 
 namespace {
 
-// Composed read windows back to the original inputs, one iteration at a time
+// Composed read windows back to the sweep's inputs, one iteration at a time
 // (reference core.py:794-835 on bounding boxes; output j feeds input j,
-// core.py:342-360).
-void grow_boxes(Planner* plan, int iterations) {
+// core.py:342-360).  A fresh composition starts from the zero box for every input, a
+// resumed one (Planner::resumed) from what each input's region lacks beyond the margins
+// all inputs share.
+void grow_boxes(Planner* plan, Growth* g, int iterations) {
   const soda_hip_program& p = plan->prog;
   const int nt = n_tensors(p);
-  if (plan->boxes.empty()) {
-    plan->feed.assign(p.n_inputs, Box{});
-    for (auto& b : plan->feed) b.set = true;
+  if (g->boxes.empty()) {
+    g->feed = g->start;
+    g->feed.resize(p.n_inputs, Box{});
+    for (auto& b : g->feed) b.set = true;
   }
-  while ((int)plan->boxes.size() < iterations) {
+  while ((int)g->boxes.size() < iterations) {
     std::vector<Box> cur(nt, Box{});
-    for (int i = 0; i < p.n_inputs; ++i) cur[i] = plan->feed[i];
+    for (int i = 0; i < p.n_inputs; ++i) cur[i] = g->feed[i];
     for (int s = 0; s < p.n_stages; ++s) {
       const int t = p.n_inputs + s;
       Box acc{};
@@ -73,20 +76,26 @@ void grow_boxes(Planner* plan, int iterations) {
       cur[t] = acc;
     }
     if (p.n_inputs == p.n_outputs)
-      for (int j = 0; j < p.n_inputs; ++j) plan->feed[j] = cur[p.output_tensor[j]];
-    plan->boxes.push_back(cur);
+      for (int j = 0; j < p.n_inputs; ++j) g->feed[j] = cur[p.output_tensor[j]];
+    g->boxes.push_back(cur);
   }
 }
 
-}  // namespace
-
-// hull over the outputs after `iterations` iterations, as positive margins
-void output_margins(Planner* plan, int iterations, int32_t* lo, int32_t* hi) {
+// hull over the outputs after `iterations` iterations of the composition `g`, as positive
+// margins; level 0 = the hull over the inputs the composition starts from
+void hull_margins(Planner* plan, Growth* g, int iterations, int32_t* lo, int32_t* hi) {
   const soda_hip_program& p = plan->prog;
   for (int d = 0; d < SODA_HIP_MAX_DIMS; ++d) lo[d] = hi[d] = 0;
-  if (iterations <= 0) return;
-  grow_boxes(plan, iterations);
-  const std::vector<Box>& b = plan->boxes[iterations - 1];
+  if (iterations <= 0) {
+    for (const Box& b : g->start)
+      for (int d = 0; d < p.dim; ++d) {
+        lo[d] = std::max(lo[d], -b.lo[d]);
+        hi[d] = std::max(hi[d], b.hi[d]);
+      }
+    return;
+  }
+  grow_boxes(plan, g, iterations);
+  const std::vector<Box>& b = g->boxes[iterations - 1];
   for (int j = 0; j < p.n_outputs; ++j) {
     const Box& o = b[p.output_tensor[j]];
     for (int d = 0; d < p.dim; ++d) {
@@ -94,6 +103,26 @@ void output_margins(Planner* plan, int iterations, int32_t* lo, int32_t* hi) {
       hi[d] = std::max(hi[d], o.hi[d]);
     }
   }
+}
+
+}  // namespace
+
+// hull over the outputs after `iterations` iterations of a fresh run, as positive margins
+void output_margins(Planner* plan, int iterations, int32_t* lo, int32_t* hi) {
+  hull_margins(plan, &plan->fresh, iterations, lo, hi);
+}
+
+// the same per output: output j of a fresh run lives on [lo[j][d], dims[d] - hi[j][d])
+void field_margins(Planner* plan, int iterations, int32_t (*lo)[SODA_HIP_MAX_DIMS],
+                   int32_t (*hi)[SODA_HIP_MAX_DIMS]) {
+  const soda_hip_program& p = plan->prog;
+  if (iterations > 0) grow_boxes(plan, &plan->fresh, iterations);
+  for (int j = 0; j < p.n_outputs; ++j)
+    for (int d = 0; d < SODA_HIP_MAX_DIMS; ++d) {
+      const bool grown = iterations > 0 && d < p.dim;
+      lo[j][d] = grown ? -plan->fresh.boxes[iterations - 1][p.output_tensor[j]].lo[d] : 0;
+      hi[j][d] = grown ? plan->fresh.boxes[iterations - 1][p.output_tensor[j]].hi[d] : 0;
+    }
 }
 
 namespace {
@@ -576,13 +605,14 @@ bool plans_fused(const Planner* plan, const std::vector<int>& fused, const int64
   return true;
 }
 
-// the box of level `level` on arrays whose valid region carries the margins vlo / vhi
-soda_hip_args box_of_level(Planner* plan, const int64_t* dims, const int32_t* vlo,
+// the box of level `level` - the intersection of the outputs' boxes - on arrays whose inputs
+// all carry the margins vlo / vhi and, beyond them, what the composition `g` starts from
+soda_hip_args box_of_level(Planner* plan, Growth* g, const int64_t* dims, const int32_t* vlo,
                            const int32_t* vhi, int level, int32_t* mlo, int32_t* mhi) {
   const soda_hip_program& p = plan->prog;
   soda_hip_args a;
   memset(&a, 0, sizeof a);
-  output_margins(plan, level, mlo, mhi);
+  hull_margins(plan, g, level, mlo, mhi);
   for (int d = 0; d < SODA_HIP_MAX_DIMS; ++d) {
     a.dims[d] = d < p.dim ? dims[d] : 1;
     a.box_lo[d] = d < p.dim ? vlo[d] + mlo[d] : 0;
@@ -597,7 +627,7 @@ soda_hip_args box_of_level(Planner* plan, const int64_t* dims, const int32_t* vl
 // x100 = 5 x depth 20 rather than 4 x depth 24 + a memory-bound depth-4 tail.
 // Kernels without cost figures: greedy, deepest first.  A split the tuner or the
 // caller fixed for these arguments (Planner::tuned_split) goes before both.
-int split_iterate(Planner* plan, const std::vector<int>& fused, const int64_t* dims,
+int split_iterate(Planner* plan, Growth* g, const std::vector<int>& fused, const int64_t* dims,
                   int iterate, const int32_t* vlo, const int32_t* vhi, std::vector<int>* seq) {
   std::vector<int> usable;
   std::vector<double> price;
@@ -607,7 +637,7 @@ int split_iterate(Planner* plan, const std::vector<int>& fused, const int64_t* d
     Launch l;
     bool empty = false;
     int32_t mlo[SODA_HIP_MAX_DIMS], mhi[SODA_HIP_MAX_DIMS];
-    int rc = make_launch(plan, k, box_of_level(plan, dims, vlo, vhi, plan->kernels[k].depth,
+    int rc = make_launch(plan, k, box_of_level(plan, g, dims, vlo, vhi, plan->kernels[k].depth,
                                                mlo, mhi), &l, &empty);
     if (rc) return rc;
     if (plan->bias_depth == plan->kernels[k].depth) l.est_us *= plan->bias;
@@ -708,14 +738,14 @@ std::vector<Buffer> sweep_inputs(const Planner* plan) {
 }
 
 // every output on ITS box of level `level`, as extras against the hull `a`
-int pack_output_extras(const Planner* plan, const soda_hip_kernel& desc, int level,
-                       const int32_t* mlo, const int32_t* mhi, soda_hip_args* a) {
+int pack_output_extras(const Planner* plan, const Growth* g, const soda_hip_kernel& desc,
+                       int level, const int32_t* mlo, const int32_t* mhi, soda_hip_args* a) {
   const soda_hip_program& p = plan->prog;
   const int dim = p.dim;
   if (p.n_outputs > max_extra_outputs(dim))
     return fail(SODA_HIP_ERR_INTERNAL, "kernel %s: %d outputs, the launch arguments "
                 "carry the boxes of %d", desc.name, p.n_outputs, max_extra_outputs(dim));
-  const std::vector<Box>& boxes = plan->boxes[level - 1];
+  const std::vector<Box>& boxes = g->boxes[level - 1];
   for (int j = 0; j < p.n_outputs; ++j) {
     const Box& o = boxes[p.output_tensor[j]];
     int64_t ex[6];
@@ -742,7 +772,7 @@ int pack_output_extras(const Planner* plan, const soda_hip_kernel& desc, int lev
 }
 
 // the launches of the split `seq` (kernel indices, one per step)
-int fused_list(Planner* plan, const std::vector<int>& fused, const std::vector<int>& seq,
+int fused_list(Planner* plan, Growth* g, const std::vector<int>& fused, const std::vector<int>& seq,
                const int64_t* dims, const int32_t* vlo, const int32_t* vhi,
                std::vector<Launch>* list, int* max_depth_used, ScratchNeeds* needs) {
   const int m = (int)seq.size();
@@ -754,8 +784,8 @@ int fused_list(Planner* plan, const std::vector<int>& fused, const std::vector<i
     route(plan, i, m, &src, tensor, needs);
     int32_t mlo[SODA_HIP_MAX_DIMS], mhi[SODA_HIP_MAX_DIMS];
     int32_t plo[SODA_HIP_MAX_DIMS], phi[SODA_HIP_MAX_DIMS];
-    output_margins(plan, done, plo, phi);
-    soda_hip_args a = box_of_level(plan, dims, vlo, vhi, done + desc.depth, mlo, mhi);
+    hull_margins(plan, g, done, plo, phi);
+    soda_hip_args a = box_of_level(plan, g, dims, vlo, vhi, done + desc.depth, mlo, mhi);
     int32_t reach_lo[SODA_HIP_MAX_DIMS], reach_hi[SODA_HIP_MAX_DIMS];
     for (int d = 0; d < SODA_HIP_MAX_DIMS; ++d) {
       reach_lo[d] = mlo[d] - plo[d];
@@ -764,7 +794,7 @@ int fused_list(Planner* plan, const std::vector<int>& fused, const std::vector<i
     int rc = check_box_inside(plan, a, reach_lo, reach_hi);
     if (rc) return rc;
     if (takes_output_extras(plan, desc)) {
-      rc = pack_output_extras(plan, desc, done + desc.depth, mlo, mhi, &a);
+      rc = pack_output_extras(plan, g, desc, done + desc.depth, mlo, mhi, &a);
       if (rc) return rc;
     }
     Launch l;
@@ -802,7 +832,7 @@ int fused_list(Planner* plan, const std::vector<int>& fused, const std::vector<i
 }
 
 // per-stage kernels: one launch per stage per iteration, intermediates in HBM
-int staged_list(Planner* plan, const int64_t* dims, int iterate, const int32_t* vlo,
+int staged_list(Planner* plan, const Growth* g, const int64_t* dims, int iterate, const int32_t* vlo,
                 const int32_t* vhi, std::vector<Launch>* list, int* max_depth_used,
                 ScratchNeeds* needs) {
   const soda_hip_program& p = plan->prog;
@@ -829,7 +859,7 @@ int staged_list(Planner* plan, const int64_t* dims, int iterate, const int32_t* 
     memset(&a, 0, sizeof a);
     for (int d = 0; d < SODA_HIP_MAX_DIMS; ++d) a.dims[d] = d < p.dim ? dims[d] : 1;
     for (int s = 0; s < p.n_stages; ++s) {
-      const Box& b = plan->boxes[it][p.n_inputs + s];
+      const Box& b = g->boxes[it][p.n_inputs + s];
       for (int d = 0; d < SODA_HIP_MAX_DIMS; ++d) {
         a.box_lo[d] = d < p.dim ? vlo[d] - b.lo[d] : 0;
         a.box_hi[d] = d < p.dim ? dims[d] - vhi[d] - b.hi[d] : 1;
@@ -854,31 +884,73 @@ int staged_list(Planner* plan, const int64_t* dims, int iterate, const int32_t* 
 
 }  // namespace
 
-int build_schedule(Planner* plan, const int64_t* dims, int iterate, const int32_t* valid_lo,
-                   const int32_t* valid_hi, std::vector<Launch>* list, int* max_depth_used,
-                   ScratchNeeds* needs) {
+int build_schedule_fields(Planner* plan, const int64_t* dims, int iterate,
+                          const int32_t (*valid_lo)[SODA_HIP_MAX_DIMS],
+                          const int32_t (*valid_hi)[SODA_HIP_MAX_DIMS],
+                          std::vector<Launch>* list, int* max_depth_used, ScratchNeeds* needs) {
   const soda_hip_program& p = plan->prog;
   if (iterate < 1) return fail(SODA_HIP_ERR_CONSTRAINT, "iterate must be >= 1");
   if (iterate > 1 && p.n_inputs != p.n_outputs)
     return fail(SODA_HIP_ERR_CONSTRAINT,
                 "iterate > 1 needs as many outputs as inputs (%d vs %d)",
                 p.n_inputs, p.n_outputs);
+  // The margins every input shares move the boxes as a whole (vlo / vhi: all there is
+  // when one margin holds for every input); what an input's region lacks beyond them is
+  // where the composition starts for it.
   int32_t vlo[SODA_HIP_MAX_DIMS] = {0, 0, 0, 0}, vhi[SODA_HIP_MAX_DIMS] = {0, 0, 0, 0};
+  std::vector<int32_t> beyond;      // per input: lo of every dimension, then hi
   for (int d = 0; d < p.dim; ++d) {
-    if (valid_lo) vlo[d] = valid_lo[d];
-    if (valid_hi) vhi[d] = valid_hi[d];
     if (dims[d] <= 0) return fail(SODA_HIP_ERR_CONSTRAINT, "dims[%d] = %lld", d,
                                   (long long)dims[d]);
+    for (int j = 0; j < p.n_inputs; ++j) {
+      const int32_t lo = valid_lo ? valid_lo[j][d] : 0, hi = valid_hi ? valid_hi[j][d] : 0;
+      vlo[d] = j ? std::min(vlo[d], lo) : lo;
+      vhi[d] = j ? std::min(vhi[d], hi) : hi;
+    }
   }
-  grow_boxes(plan, iterate);
+  bool uniform = true;
+  for (int j = 0; j < p.n_inputs; ++j)
+    for (int side = 0; side < 2; ++side)
+      for (int d = 0; d < p.dim; ++d) {
+        const int32_t* v = side ? (valid_hi ? valid_hi[j] : nullptr)
+                                : (valid_lo ? valid_lo[j] : nullptr);
+        beyond.push_back((v ? v[d] : 0) - (side ? vhi[d] : vlo[d]));
+        uniform = uniform && beyond.back() == 0;
+      }
+  Growth* g = &plan->fresh;
+  if (!uniform) {
+    g = &plan->resumed[beyond];
+    if (g->start.empty()) {
+      g->start.assign(p.n_inputs, Box{});
+      for (int j = 0; j < p.n_inputs; ++j)
+        for (int d = 0; d < p.dim; ++d) {
+          g->start[j].lo[d] = -beyond[(2 * j) * p.dim + d];
+          g->start[j].hi[d] = beyond[(2 * j + 1) * p.dim + d];
+        }
+    }
+  }
+  grow_boxes(plan, g, iterate);
   list->clear();
   *max_depth_used = 0;
   *needs = ScratchNeeds{};
   const std::vector<int> fused = eligible_fused(plan, dims);
   if (!plans_fused(plan, fused, dims, iterate))
-    return staged_list(plan, dims, iterate, vlo, vhi, list, max_depth_used, needs);
+    return staged_list(plan, g, dims, iterate, vlo, vhi, list, max_depth_used, needs);
   std::vector<int> seq;
-  int rc = split_iterate(plan, fused, dims, iterate, vlo, vhi, &seq);
+  int rc = split_iterate(plan, g, fused, dims, iterate, vlo, vhi, &seq);
   if (rc) return rc;
-  return fused_list(plan, fused, seq, dims, vlo, vhi, list, max_depth_used, needs);
+  return fused_list(plan, g, fused, seq, dims, vlo, vhi, list, max_depth_used, needs);
+}
+
+// one margin for every input
+int build_schedule(Planner* plan, const int64_t* dims, int iterate, const int32_t* valid_lo,
+                   const int32_t* valid_hi, std::vector<Launch>* list, int* max_depth_used,
+                   ScratchNeeds* needs) {
+  int32_t lo[SODA_HIP_MAX_IO][SODA_HIP_MAX_DIMS], hi[SODA_HIP_MAX_IO][SODA_HIP_MAX_DIMS];
+  for (int j = 0; j < SODA_HIP_MAX_IO; ++j)
+    for (int d = 0; d < SODA_HIP_MAX_DIMS; ++d) {
+      lo[j][d] = valid_lo && d < plan->prog.dim ? valid_lo[d] : 0;
+      hi[j][d] = valid_hi && d < plan->prog.dim ? valid_hi[d] : 0;
+    }
+  return build_schedule_fields(plan, dims, iterate, lo, hi, list, max_depth_used, needs);
 }

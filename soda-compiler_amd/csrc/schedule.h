@@ -54,6 +54,15 @@ struct ScratchNeeds {
   bool locals = false;     // LOCAL
 };
 
+// Composed boxes per iteration per tensor, grown on demand, from the boxes the inputs
+// start on (lo <= 0 <= hi, relative to the margins all inputs share; empty = the zero
+// box for every input: a fresh run, or one margin for all).
+struct Growth {
+  std::vector<Box> start;
+  std::vector<std::vector<Box>> boxes;
+  std::vector<Box> feed;
+};
+
 struct Planner {
   soda_hip_program prog{};
   std::vector<soda_hip_kernel> kernels;
@@ -79,9 +88,12 @@ struct Planner {
   double bias = 1.0;
   bool tuning = false;               // candidates are being timed: ignore tuned_split
   // memo tables
-  // composed boxes per iteration per stage, grown on demand
-  std::vector<std::vector<Box>> boxes;
-  std::vector<Box> feed;
+  // composed boxes of a run from inputs that share their region (Growth)
+  Growth fresh;
+  // ... and of resumed runs whose inputs differ, keyed by what each input's region lacks
+  // beyond the shared margins (per input: lo of every dimension, then hi), so that
+  // different starts do not collide
+  std::map<std::vector<int32_t>, Growth> resumed;
   // XCD super-tile shape chosen per (kernel, tiles along x, y, chunks): the search
   // walks every super-tile and a sweep's launches mostly repeat a few grids
   mutable std::map<std::array<int64_t, 4>, std::pair<int, int>> xcd_shape;
@@ -113,8 +125,11 @@ const char* tuning_env(const char* name);
 int n_tensors(const soda_hip_program& p);
 bool is_output_tensor(const soda_hip_program& p, int t);
 
-// hull over the outputs after `iterations` iterations, as positive margins
+// hull over the outputs after `iterations` iterations of a fresh run, as positive margins
 void output_margins(Planner* plan, int iterations, int32_t* lo, int32_t* hi);
+// the same per output (n_outputs rows)
+void field_margins(Planner* plan, int iterations, int32_t (*lo)[SODA_HIP_MAX_DIMS],
+                   int32_t (*hi)[SODA_HIP_MAX_DIMS]);
 
 // the key of Planner::tuned_split
 std::array<int64_t, 5> split_key(const Planner* plan, const int64_t* dims, int iterate);
@@ -131,6 +146,13 @@ const double kBeyondCacheBytes = 288.0 * 1024 * 1024;
 int build_schedule(Planner* plan, const int64_t* dims, int iterate, const int32_t* valid_lo,
                    const int32_t* valid_hi, std::vector<Launch>* list, int* max_depth_used,
                    ScratchNeeds* needs);
+// The same with a valid region per input: valid_lo / valid_hi hold n_inputs rows of
+// margins (NULL = none).  Output j of the sweep is defined on the box the composition
+// gives from those regions; no output is defined outside the margins all inputs share.
+int build_schedule_fields(Planner* plan, const int64_t* dims, int iterate,
+                          const int32_t (*valid_lo)[SODA_HIP_MAX_DIMS],
+                          const int32_t (*valid_hi)[SODA_HIP_MAX_DIMS],
+                          std::vector<Launch>* list, int* max_depth_used, ScratchNeeds* needs);
 
 #pragma GCC visibility pop
 

@@ -47,8 +47,10 @@ struct SlabGeometry {
 
 int slab_geometry(const soda_hip_plan* plan, const soda_hip_slab* s, SlabGeometry* g) {
   const soda_hip_program& p = plan->prog;
-  if (p.n_inputs != 1 || p.n_outputs != 1)
-    return fail(SODA_HIP_ERR_CONSTRAINT, "slabs: one-input one-output programs");
+  // the geometry is the same for every field of a program over several (output j feeds
+  // input j); which driver runs it is the drivers' check
+  if (p.n_inputs != p.n_outputs)
+    return fail(SODA_HIP_ERR_CONSTRAINT, "slabs: programs with as many outputs as inputs");
   if (s->world < 1 || s->rank < 0 || s->rank >= s->world || s->exchange < 1 ||
       s->reach_lo < 0 || s->reach_hi < 0)
     return fail(SODA_HIP_ERR_CONSTRAINT, "slab descriptor out of range");
@@ -109,7 +111,8 @@ struct RecutTable {
 int recut_table(const soda_hip_plan* plan, const soda_hip_slab* s, int iterate, RecutTable* t) {
   const soda_hip_program& p = plan->prog;
   if (p.n_inputs != 1 || p.n_outputs != 1)
-    return fail(SODA_HIP_ERR_CONSTRAINT, "slabs: one-input one-output programs");
+    return fail(SODA_HIP_ERR_CONSTRAINT, "slabs: static cut only for programs over several "
+                "fields");
   if (s->world < 1 || s->rank < 0 || s->rank >= s->world || s->exchange < 1 ||
       s->reach_lo < 0 || s->reach_hi < 0 || iterate < 1)
     return fail(SODA_HIP_ERR_CONSTRAINT, "slab descriptor out of range");
@@ -257,6 +260,9 @@ int soda_hip_run_slab(soda_hip_plan* plan, const soda_hip_slab* slab, void* comm
                       void** result, int* exchanges) {
   if (!plan || !slab || !a || !b || !c || !result)
     return fail(SODA_HIP_ERR_NULL_ARGUMENT, "NULL argument");
+  if (plan->prog.n_inputs != 1 || plan->prog.n_outputs != 1)
+    return fail(SODA_HIP_ERR_CONSTRAINT, "slabs: one-input one-output programs (programs "
+                "over several fields: soda_hip_run_slab_fields)");
   if (slab->world > 1 && !comm)
     return fail(SODA_HIP_ERR_NULL_ARGUMENT, "world %d needs an RCCL communicator", slab->world);
   if (slab->world > 1 && !rccl().ok)
@@ -505,6 +511,135 @@ int soda_hip_run_slab(soda_hip_plan* plan, const soda_hip_slab* slab, void* comm
   if (!rc) rc = ghosts_have_landed();
   if (rc) return give_up(rc);
   *result = src;
+  if (exchanges) *exchanges = count;
+  return 0;
+}
+
+int soda_hip_run_slab_fields(soda_hip_plan* plan, const soda_hip_slab* slab, void* comm,
+                             void* const* a, void* const* b, void* const* c, int iterate,
+                             void* stream, void** result, int* exchanges) {
+  if (!plan || !slab || !a || !b || !c || !result)
+    return fail(SODA_HIP_ERR_NULL_ARGUMENT, "NULL argument");
+  const soda_hip_program& p = plan->prog;
+  const int n = p.n_inputs;
+  for (int j = 0; j < n; ++j)
+    if (!a[j] || !b[j] || !c[j])
+      return fail(SODA_HIP_ERR_NULL_ARGUMENT, "an array of field %d is NULL", j);
+  if (slab->world > 1 && !comm)
+    return fail(SODA_HIP_ERR_NULL_ARGUMENT, "world %d needs an RCCL communicator", slab->world);
+  if (slab->world > 1 && !rccl().ok)
+    return fail(SODA_HIP_ERR_NO_DEVICE, "librccl.so could not be loaded: %s", dlerror());
+  // as soda_hip_run_slab: whatever is wrong with the call itself is found before the
+  // first message is enqueued and leaves the communicator alone
+  if (iterate < 1) return fail(SODA_HIP_ERR_CONSTRAINT, "iterate must be >= 1");
+  if (slab->cut != SODA_HIP_SLAB_CUT_STATIC)
+    return fail(SODA_HIP_ERR_CONSTRAINT, "slabs: static cut only for programs over several "
+                "fields");
+  if (slab->order != SODA_HIP_SLAB_SERIAL)
+    return fail(SODA_HIP_ERR_CONSTRAINT, "slabs: serial order only for programs over several "
+                "fields");
+  SlabGeometry g{};
+  int rc = slab_geometry(plan, slab, &g);
+  if (rc) return rc;
+  const int last = p.dim - 1;
+  int64_t row_bytes[SODA_HIP_MAX_IO];
+  for (int j = 0; j < n; ++j) {
+    // field j's three arrays hold input j and output j in turn
+    if (p.elem_size[j] != p.elem_size[p.output_tensor[j]])
+      return fail(SODA_HIP_ERR_CONSTRAINT, "slabs: output %d (%d bytes per cell) cannot feed "
+                  "input %d (%d)", j, p.elem_size[p.output_tensor[j]], j, p.elem_size[j]);
+    row_bytes[j] = p.elem_size[j];
+    for (int d = 0; d < last; ++d) row_bytes[j] *= slab->dims[d];
+  }
+  // the ghost rows must cover what ANY field reads in `exchange` iterations: the composed
+  // margin of a field after k iterations is at most k x the hull of one iteration's
+  {
+    int32_t lo[SODA_HIP_MAX_DIMS], hi[SODA_HIP_MAX_DIMS];
+    output_margins(plan, 1, lo, hi);
+    if (slab->world > 1 && (slab->reach_lo < lo[last] || slab->reach_hi < hi[last]))
+      return fail(SODA_HIP_ERR_CONSTRAINT, "slab reach %d / %d is below the program's %d / %d "
+                  "(soda_hip_plan_margins(plan, 1))", slab->reach_lo, slab->reach_hi,
+                  (int)lo[last], (int)hi[last]);
+  }
+  bool rccl_failed = false;
+  auto give_up = [&](int e) {
+    if (e && !rccl_failed && slab->abort_on_error && slab->world > 1 && comm &&
+        rccl().comm_abort) {
+      const std::string keep = g_last_error;
+      (void)rccl().comm_abort(comm);
+      g_last_error = keep + " (communicator aborted)";
+    }
+    return e;
+  };
+  hipStream_t s = as_stream(stream);
+  int64_t local_dims[SODA_HIP_MAX_DIMS] = {1, 1, 1, 1};
+  for (int d = 0; d < p.dim; ++d) local_dims[d] = slab->dims[d];
+  local_dims[last] = g.extent;
+  const int64_t send_down = g.has_lo ? (int64_t)slab->exchange * slab->reach_hi : 0;
+  const int64_t send_up = g.has_hi ? (int64_t)slab->exchange * slab->reach_lo : 0;
+  const int64_t first_own = g.ghost_lo, last_own = g.ghost_lo + g.own;
+  // ONE group per super-step carries every field's ghost rows; the rows of one field are
+  // contiguous, so nothing is packed: four messages per field at most, field by field
+  // (both sides of a pair enumerate the fields in the same order)
+  auto exchange = [&](void* const* arrays) -> int {
+    if (slab->world == 1) return 0;
+    const Rccl& r = rccl();
+    int e = r.group_start();
+    for (int j = 0; j < n && !e; ++j) {
+      char* at = (char*)arrays[j];
+      const int64_t rb = row_bytes[j];
+      if (!e && g.has_lo && send_down)
+        e = r.send(at + first_own * rb, (size_t)(send_down * rb), 0, slab->rank - 1, comm, s);
+      if (!e && g.has_lo && g.ghost_lo)
+        e = r.recv(at, (size_t)(g.ghost_lo * rb), 0, slab->rank - 1, comm, s);
+      if (!e && g.has_hi && send_up)
+        e = r.send(at + (last_own - send_up) * rb, (size_t)(send_up * rb), 0, slab->rank + 1,
+                   comm, s);
+      if (!e && g.has_hi && g.ghost_hi)
+        e = r.recv(at + last_own * rb, (size_t)(g.ghost_hi * rb), 0, slab->rank + 1, comm, s);
+    }
+    const int e2 = r.group_end();
+    if (e || e2) {
+      rccl_failed = true;
+      return fail(SODA_HIP_ERR_DEVICE_RUN, "RCCL ghost exchange failed: %s",
+                  r.error_string ? r.error_string(e ? e : e2) : "?");
+    }
+    return 0;
+  };
+  int fail_rank = -1, fail_at = -1;      // test hook, as in soda_hip_run_slab
+  if (const char* env = tuning_env("SODA_HIP_FAIL_RANK")) fail_rank = atoi(env);
+  if (const char* env = tuning_env("SODA_HIP_FAIL_SUPERSTEP")) fail_at = atoi(env);
+  void* src[SODA_HIP_MAX_IO];
+  void* dst[SODA_HIP_MAX_IO];
+  for (int j = 0; j < n; ++j) src[j] = a[j];
+  int done = 0, k = 0, count = 0;
+  while (done < iterate && !rc) {
+    rc = exchange(src);
+    count += slab->world > 1;
+    if (rc) break;
+    const int step = std::min(slab->exchange, iterate - done);
+    // every field's own valid region: sides cut inside valid rows are fully valid, the
+    // global sides - of every dimension - carry the field's own margin after `done`
+    // iterations (output j fed input j)
+    int32_t lo[SODA_HIP_MAX_IO][SODA_HIP_MAX_DIMS], hi[SODA_HIP_MAX_IO][SODA_HIP_MAX_DIMS];
+    field_margins(plan, done, lo, hi);
+    for (int j = 0; j < n; ++j) {
+      if (g.has_lo) lo[j][last] = 0;
+      if (g.has_hi) hi[j][last] = 0;
+      dst[j] = k % 2 ? c[j] : b[j];
+    }
+    if (slab->rank == fail_rank && k == fail_at) {
+      rc = fail(SODA_HIP_ERR_DEVICE_RUN, "injected failure of rank %d at super-step %d",
+                fail_rank, fail_at);
+      break;
+    }
+    rc = soda_hip_sweep_fields(plan, src, dst, local_dims, step, lo, hi, stream);
+    for (int j = 0; j < n; ++j) src[j] = dst[j];
+    done += step;
+    ++k;
+  }
+  if (rc) return give_up(rc);
+  for (int j = 0; j < n; ++j) result[j] = src[j];
   if (exchanges) *exchanges = count;
   return 0;
 }

@@ -81,8 +81,9 @@ void* resolve(const soda_hip_plan* plan, Buffer b, void* const* in, void* const*
 // The launch list of one sweep over the caller's arrays, ready to launch: planned,
 // the plan-owned arrays it names allocated (and zeroed on `stream`), buffers bound.
 int bound_schedule(soda_hip_plan* plan, void* const* in, void* const* out,
-                   const int64_t* dims, int iterate, const int32_t* valid_lo,
-                   const int32_t* valid_hi, std::vector<Launch>* list,
+                   const int64_t* dims, int iterate,
+                   const int32_t (*valid_lo)[SODA_HIP_MAX_DIMS],
+                   const int32_t (*valid_hi)[SODA_HIP_MAX_DIMS], std::vector<Launch>* list,
                    int* max_depth_used, hipStream_t stream) {
   const soda_hip_program& p = plan->prog;
   for (int j = 0; j < p.n_inputs; ++j)
@@ -90,7 +91,8 @@ int bound_schedule(soda_hip_plan* plan, void* const* in, void* const* out,
   for (int j = 0; j < p.n_outputs; ++j)
     if (!out[j]) return fail(SODA_HIP_ERR_NULL_ARGUMENT, "output %d is NULL", j);
   ScratchNeeds needs;
-  int rc = build_schedule(plan, dims, iterate, valid_lo, valid_hi, list, max_depth_used, &needs);
+  int rc = build_schedule_fields(plan, dims, iterate, valid_lo, valid_hi, list, max_depth_used,
+                                 &needs);
   if (rc) return rc;
   rc = ensure_scratch(plan, dims, needs, stream);
   if (rc) return rc;
@@ -98,6 +100,16 @@ int bound_schedule(soda_hip_plan* plan, void* const* in, void* const* out,
     for (int t = 0; t < n_tensors(p); ++t) l.args.tensor[t] = resolve(plan, l.buffer[t], in, out);
   return 0;
 }
+
+// one margin (NULL = none) as the margin of every input
+struct Repeated {
+  int32_t rows[SODA_HIP_MAX_IO][SODA_HIP_MAX_DIMS];
+  Repeated(const soda_hip_plan* plan, const int32_t* margin) {
+    for (int j = 0; j < SODA_HIP_MAX_IO; ++j)
+      for (int d = 0; d < SODA_HIP_MAX_DIMS; ++d)
+        rows[j][d] = margin && d < plan->prog.dim ? margin[d] : 0;
+  }
+};
 
 int launch_one(const soda_hip_plan* plan, const Launch& l, hipStream_t stream) {
   const soda_hip_kernel& desc = plan->kernels[l.kernel];
@@ -498,6 +510,19 @@ int soda_hip_plan_margins(const soda_hip_plan* plan, int iterations,
   return 0;
 }
 
+int soda_hip_plan_field_margins(const soda_hip_plan* plan, int iterations,
+                                int32_t (*lo)[SODA_HIP_MAX_DIMS],
+                                int32_t (*hi)[SODA_HIP_MAX_DIMS]) {
+  if (!plan || !lo || !hi) return fail(SODA_HIP_ERR_NULL_ARGUMENT, "NULL argument");
+  if (iterations < 0) return fail(SODA_HIP_ERR_CONSTRAINT, "iterations < 0");
+  if (iterations > 1 && plan->prog.n_inputs != plan->prog.n_outputs)
+    return fail(SODA_HIP_ERR_CONSTRAINT,
+                "iterations > 1 need as many outputs as inputs (%d vs %d)",
+                plan->prog.n_inputs, plan->prog.n_outputs);
+  field_margins(const_cast<soda_hip_plan*>(plan), iterations, lo, hi);
+  return 0;
+}
+
 int soda_hip_plan_set_max_depth(soda_hip_plan* plan, int max_depth) {
   if (!plan) return fail(SODA_HIP_ERR_NULL_ARGUMENT, "plan is NULL");
   plan->max_depth = max_depth;
@@ -619,27 +644,40 @@ int soda_hip_plan_set_out_final_only(soda_hip_plan* plan, int on) {
   return 0;
 }
 
-int soda_hip_plan_schedule(soda_hip_plan* plan, const int64_t dims[SODA_HIP_MAX_DIMS],
-                           int iterate, const int32_t* valid_lo,
-                           const int32_t* valid_hi, int32_t* kernel_index,
-                           double* est_us, int capacity, int* n_launches) {
+int soda_hip_plan_schedule_fields(soda_hip_plan* plan, const int64_t dims[SODA_HIP_MAX_DIMS],
+                                  int iterate, const int32_t (*valid_lo)[SODA_HIP_MAX_DIMS],
+                                  const int32_t (*valid_hi)[SODA_HIP_MAX_DIMS],
+                                  int32_t* kernel_index, double* est_us, soda_hip_args* args,
+                                  int capacity, int* n_launches) {
   if (!plan || !dims || !n_launches) return fail(SODA_HIP_ERR_NULL_ARGUMENT, "NULL argument");
   std::vector<Launch> list;
   int depth = 0;
   ScratchNeeds needs;
-  int rc = build_schedule(plan, dims, iterate, valid_lo, valid_hi, &list, &depth, &needs);
+  int rc = build_schedule_fields(plan, dims, iterate, valid_lo, valid_hi, &list, &depth, &needs);
   if (rc) return rc;
   *n_launches = (int)list.size();
   for (int i = 0; i < (int)list.size() && i < capacity; ++i) {
     if (kernel_index) kernel_index[i] = list[i].kernel;
     if (est_us) est_us[i] = list[i].est_us;
+    if (args) args[i] = list[i].args;
   }
   return 0;
 }
 
-int soda_hip_sweep(soda_hip_plan* plan, void* const* in, void* const* out,
-                   const int64_t dims[SODA_HIP_MAX_DIMS], int iterate,
-                   const int32_t* valid_lo, const int32_t* valid_hi, void* stream) {
+int soda_hip_plan_schedule(soda_hip_plan* plan, const int64_t dims[SODA_HIP_MAX_DIMS],
+                           int iterate, const int32_t* valid_lo,
+                           const int32_t* valid_hi, int32_t* kernel_index,
+                           double* est_us, int capacity, int* n_launches) {
+  if (!plan || !dims || !n_launches) return fail(SODA_HIP_ERR_NULL_ARGUMENT, "NULL argument");
+  const Repeated lo(plan, valid_lo), hi(plan, valid_hi);
+  return soda_hip_plan_schedule_fields(plan, dims, iterate, lo.rows, hi.rows, kernel_index,
+                                       est_us, nullptr, capacity, n_launches);
+}
+
+int soda_hip_sweep_fields(soda_hip_plan* plan, void* const* in, void* const* out,
+                          const int64_t dims[SODA_HIP_MAX_DIMS], int iterate,
+                          const int32_t (*valid_lo)[SODA_HIP_MAX_DIMS],
+                          const int32_t (*valid_hi)[SODA_HIP_MAX_DIMS], void* stream) {
   if (!plan || !in || !out || !dims) return fail(SODA_HIP_ERR_NULL_ARGUMENT, "NULL argument");
   std::vector<Launch> list;
   int depth = 0;
@@ -651,6 +689,14 @@ int soda_hip_sweep(soda_hip_plan* plan, void* const* in, void* const* out,
     if (rc) return rc;
   }
   return 0;
+}
+
+int soda_hip_sweep(soda_hip_plan* plan, void* const* in, void* const* out,
+                   const int64_t dims[SODA_HIP_MAX_DIMS], int iterate,
+                   const int32_t* valid_lo, const int32_t* valid_hi, void* stream) {
+  if (!plan || !in || !out || !dims) return fail(SODA_HIP_ERR_NULL_ARGUMENT, "NULL argument");
+  const Repeated lo(plan, valid_lo), hi(plan, valid_hi);
+  return soda_hip_sweep_fields(plan, in, out, dims, iterate, lo.rows, hi.rows, stream);
 }
 
 int soda_hip_sweep_timed(soda_hip_plan* plan, void* const* in, void* const* out,
@@ -889,7 +935,7 @@ int soda_hip_run_buffers(soda_hip_plan* plan, soda_hip_buffer_t* const* inputs,
       }
       window = cur[p.output_tensor[0]];
       if (!window.set)      // the first output does not depend on the first input
-        window = plan->boxes[iterate - 1][p.output_tensor[0]];
+        window = plan->fresh.boxes[iterate - 1][p.output_tensor[0]];
     }
     for (int j = 0; j < p.n_outputs; ++j) {
       soda_hip_buffer_t* b = outputs[j];
@@ -995,7 +1041,7 @@ int soda_hip_run_buffers(soda_hip_plan* plan, soda_hip_buffer_t* const* inputs,
     int64_t lo[4] = {0, 0, 0, 0}, hi[4] = {1, 1, 1, 1}, ext[4] = {1, 1, 1, 1};
     bool empty = false;
     // each output has its own composed window (host.py:1082-1091)
-    const Box& ob = plan->boxes[iterate - 1][p.output_tensor[j]];
+    const Box& ob = plan->fresh.boxes[iterate - 1][p.output_tensor[j]];
     for (int d = 0; d < p.dim; ++d) {
       lo[d] = -ob.lo[d]; hi[d] = dims[d] - ob.hi[d]; ext[d] = dims[d];
       if (hi[d] <= lo[d]) empty = true;

@@ -163,6 +163,16 @@ def print_selfcheck(spec, out):
   w('  return error_count;\n}\n\n')
 
 
+def slabs_over_fields(spec):
+  """Whether the program runs as slabs through soda_hip_run_slab_fields: several fields,
+  output j feeding input j with the same element type."""
+  types = specmod.tensor_c_types(spec)
+  ins = [t['name'] for t in spec['inputs']]
+  outs = list(spec['outputs'])
+  return len(ins) == len(outs) > 1 and all(
+      specmod.ELEM_SIZE[types[i]] == specmod.ELEM_SIZE[types[o]] for i, o in zip(ins, outs))
+
+
 def print_multi_gpu(spec, w, app, name_in, name_out, dim, deepest):
   """`<app>_multi_gpu`: the grid cut into slabs along the outermost dimension,
   all GPUs of the node driven from ONE process, one thread per GPU
@@ -321,6 +331,152 @@ def print_multi_gpu(spec, w, app, name_in, name_out, dim, deepest):
   w('  for (int rc : status) if (rc) return rc;\n')
   w('  return 0;\n}\n#endif  // SODA_HIP_MULTI_GPU\n\n')
 
+def print_multi_gpu_fields(spec, w, app, ins, outs, dim, deepest):
+  """`<app>_multi_gpu` of a program over several fields (output j feeds input j): as
+  print_multi_gpu, with three device arrays PER FIELD and soda_hip_run_slab_fields - the
+  static cut in the serial order, the only ones that driver takes.  Every output's own
+  box of the valid interior is written back."""
+  n = len(ins)
+  w('#ifdef SODA_HIP_MULTI_GPU\n#include <rccl/rccl.h>\n#include <thread>\n#include <mutex>\n#include <condition_variable>\n'
+    '#include <vector>\n')
+  w('extern "C" int %s_multi_gpu(%sconst char* blob, int iterate, int ngpu) {\n' % (
+      app, ''.join('buffer_t* var_%s_buffer, ' % v for v in ins + outs)))
+  w('  const int dim = %d, last = dim - 1, n_fields = %d;\n' % (dim, n))
+  w('  int count = 0;\n  soda_hip_device_count(&count);\n')
+  w('  const bool rehearse = getenv("SODA_HIP_REHEARSE_RANKS_ON_ONE_GPU") != nullptr;\n')
+  w('  if (count < 1) return SODA_HIP_ERR_NO_DEVICE;\n')
+  w('  if (ngpu > count && !rehearse) ngpu = count;\n')
+  w('  if (ngpu < 1) return SODA_HIP_ERR_NO_DEVICE;\n')
+  w('  buffer_t* in[] = {%s};\n' % ', '.join('var_%s_buffer' % v for v in ins))
+  w('  buffer_t* out[] = {%s};\n' % ', '.join('var_%s_buffer' % v for v in outs))
+  w('  const int64_t rows = in[0]->extent[last];\n')
+  w('  if (rows < ngpu) ngpu = (int)rows;\n')
+  w('  std::vector<ncclComm_t> comms(ngpu, nullptr);\n')
+  w('  if (ngpu > 1) {\n    std::vector<int> devs(ngpu);\n'
+    '    for (int i = 0; i < ngpu; ++i) devs[i] = i % count;\n'
+    '    if (ncclCommInitAll(comms.data(), ngpu, devs.data()) != ncclSuccess) {\n'
+    '      fprintf(*error_report, "ERROR: ncclCommInitAll failed\\n");\n'
+    '      return SODA_HIP_ERR_NO_DEVICE;\n    }\n  }\n')
+  w('  std::vector<int> status(ngpu, 0);\n')
+  # the same rendezvous and the same single owner of the communicators as print_multi_gpu
+  w('  std::mutex gate; std::condition_variable gate_cv; int arrived = 0; '
+    'bool setup_failed = false, aborted = false;\n')
+  w('  auto rendezvous = [&](bool ok) {\n'
+    '    std::unique_lock<std::mutex> lock(gate);\n'
+    '    if (!ok) setup_failed = true;\n'
+    '    if (++arrived == ngpu) gate_cv.notify_all();\n'
+    '    else gate_cv.wait(lock, [&] { return arrived == ngpu; });\n'
+    '    return !setup_failed;\n  };\n')
+  w('  auto abort_all = [&]() {\n'
+    '    std::lock_guard<std::mutex> lock(gate);\n'
+    '    if (aborted) return;\n    aborted = true;\n'
+    '    for (ncclComm_t& comm : comms) if (comm) { ncclCommAbort(comm); comm = nullptr; }\n'
+    '  };\n')
+  w('  auto worker = [&](int rank) {\n')
+  w('    int& rc = status[rank];\n')
+  w('    soda_hip_module* module = nullptr;\n    soda_hip_plan* plan = nullptr;\n')
+  w('    void *a[%d] = {}, *b[%d] = {}, *c[%d] = {}, *result[%d] = {};\n' % (n, n, n, n))
+  w('    size_t row_bytes[%d] = {};\n' % n)
+  w('    soda_hip_slab slab;\n    memset(&slab, 0, sizeof slab);\n')
+  w('    int64_t local[4] = {1, 1, 1, 1}, in_at = 0, res_first = 0, res_last = 0, '
+    'res_at = 0, own = 0;\n')
+  w('    rc = soda_hip_set_device(rank % count);\n')
+  w('    if (!rc) rc = soda_hip_module_load_file(blob, &module);\n')
+  w('    soda_hip_program program;\n    fill_program(&program);\n')
+  w('    soda_hip_kernel kernels[32];\n    const int n_kernels = fill_kernels(kernels);\n')
+  w('    if (!rc) rc = soda_hip_plan_create(module, &program, kernels, n_kernels, &plan);\n')
+  w('    if (rc == 0) {\n')
+  # the reach: the hull over the fields of one iteration's margins
+  w('      int32_t lo[4], hi[4];\n      soda_hip_plan_margins(plan, 1, lo, hi);\n')
+  w('      slab.rank = rank; slab.world = ngpu;\n')
+  w('      slab.reach_lo = lo[last]; slab.reach_hi = hi[last];\n')
+  w('      for (int d = 0; d < dim; ++d) slab.dims[d] = in[0]->extent[d];\n')
+  w('      const int64_t base = rows / ngpu, extra = rows % ngpu;\n')
+  w('      slab.own_first = rank * base + (rank < extra ? rank : extra);\n')
+  w('      slab.own_last = slab.own_first + base + (rank < extra ? 1 : 0);\n')
+  w('      const int reach = lo[last] > hi[last] ? lo[last] : hi[last];\n')
+  w('      int exchange = %d * 8;   // eight launches of the deepest fused kernel\n'
+    % deepest)
+  w('      while (exchange > %d && (int64_t)exchange * (reach > 0 ? reach : 1) * 2 * 100 > '
+    'base * 15) exchange -= %d;\n' % (deepest, deepest))
+  w('      if (exchange > iterate) exchange = iterate;\n')
+  w('      if (exchange < 1) exchange = 1;\n')
+  w('      slab.cut = SODA_HIP_SLAB_CUT_STATIC;   // the cut programs over several fields take\n')
+  w('      slab.order = SODA_HIP_SLAB_SERIAL;\n')
+  w('      slab.abort_on_error = 0;   // abort_all below owns every communicator\n')
+  w('      // never deeper than the smallest slab (all ranks compute the same value)\n')
+  w('      rc = soda_hip_slab_exchange(rows, ngpu, lo[last], hi[last], exchange, &exchange);\n')
+  w('      slab.exchange = ngpu > 1 ? exchange : iterate;\n')
+  w('      if (!rc) rc = soda_hip_slab_layout(plan, &slab, iterate, local, &in_at, &res_first, '
+    '&res_last, &res_at);\n')
+  w('      own = slab.own_last - slab.own_first;\n')
+  w('      for (int j = 0; j < n_fields && !rc; ++j) {\n')
+  w('        row_bytes[j] = (size_t)in[j]->elem_size;\n')
+  w('        for (int d = 0; d < last; ++d) row_bytes[j] *= (size_t)in[j]->extent[d];\n')
+  w('        const size_t bytes = row_bytes[j] * (size_t)local[last];\n')
+  w('        rc = soda_hip_malloc(&a[j], bytes);\n')
+  w('        if (!rc) rc = soda_hip_malloc(&b[j], bytes);\n')
+  w('        if (!rc) rc = soda_hip_malloc(&c[j], bytes);\n')
+  w('        if (!rc) rc = soda_hip_memset(a[j], 0, bytes, nullptr);\n')
+  w('        if (!rc) rc = soda_hip_memset(b[j], 0, bytes, nullptr);\n')
+  w('        if (!rc) rc = soda_hip_memset(c[j], 0, bytes, nullptr);\n')
+  w('        if (!rc) rc = soda_hip_memcpy_h2d((char*)a[j] + in_at * row_bytes[j], '
+    'in[j]->host + slab.own_first * row_bytes[j], own * row_bytes[j], nullptr);\n')
+  w('      }\n')
+  w('      if (!rc) rc = soda_hip_stream_synchronize(nullptr);\n')
+  w('    }\n')
+  w('    if (rc) fprintf(*error_report, "ERROR: GPU %d: %s: %s\\n", rank, '
+    'soda_hip_error_name(rc), soda_hip_last_error());\n')
+  w('    // nobody sends before everybody is ready to receive\n')
+  w('    const bool go = rendezvous(rc == 0);\n')
+  w('    if (!go && !rc) rc = SODA_HIP_ERR_GENERIC;   // a peer failed during set-up\n')
+  w('    if (go) {\n')
+  w('      rc = soda_hip_run_slab_fields(plan, &slab, comms[rank], a, b, c, iterate, '
+    'nullptr, result, nullptr);\n')
+  w('      if (!rc) rc = soda_hip_stream_synchronize(nullptr);\n')
+  w('      if (rc) {\n')
+  w('        fprintf(*error_report, "ERROR: GPU %d: %s: %s\\n", rank, '
+    'soda_hip_error_name(rc), soda_hip_last_error());\n')
+  w('        if (ngpu > 1) abort_all();   // peers blocked in ncclRecv return with an error\n')
+  w('      }\n')
+  w('      // only the valid interior goes back to the caller (host.py:838-899): every\n')
+  w('      // output on its own box (host.py:1082-1091)\n')
+  w('      int32_t mlo[%d][4], mhi[%d][4];\n' % (n, n))
+  w('      if (!rc) rc = soda_hip_plan_field_margins(plan, iterate, mlo, mhi);\n')
+  w('      const int64_t held = res_last - res_first;\n')
+  w('      for (int j = 0; j < n_fields && !rc; ++j) {\n')
+  w('        const size_t rb = row_bytes[j];\n')
+  w('        std::vector<uint8_t> stage((size_t)(held > 0 ? held : 0) * rb + 1);\n')
+  w('        if (held > 0) rc = soda_hip_memcpy_d2h(stage.data(), (char*)result[j] + res_at * '
+    'rb, held * rb, nullptr);\n')
+  w('        if (!rc) rc = soda_hip_stream_synchronize(nullptr);\n')
+  w('        const int64_t es = in[j]->elem_size;\n')
+  w('        const int64_t x0 = mlo[j][0], x1 = in[j]->extent[0] - mhi[j][0];\n')
+  w('        const int64_t inner_rows = rb / (in[j]->extent[0] * es);\n')
+  w('        for (int64_t y = res_first; !rc && x1 > x0 && y < res_last; ++y) {\n')
+  w('          if (y < mlo[j][last] || y >= rows - mhi[j][last]) continue;\n')
+  w('          for (int64_t q = 0; q < inner_rows; ++q) {\n')
+  if dim == 3:
+    w('            if (q < mlo[j][1] || q >= in[j]->extent[1] - mhi[j][1]) continue;\n')
+  if dim == 4:
+    w('            const int64_t q1 = q % in[j]->extent[1], q2 = q / in[j]->extent[1];\n')
+    w('            if (q1 < mlo[j][1] || q1 >= in[j]->extent[1] - mhi[j][1] || q2 < mlo[j][2] || '
+      'q2 >= in[j]->extent[2] - mhi[j][2]) continue;\n')
+  w('            const size_t off = (size_t)(q * in[j]->extent[0] + x0) * es;\n')
+  w('            memcpy(out[j]->host + y * rb + off, stage.data() + '
+    '(y - res_first) * rb + off, (size_t)(x1 - x0) * es);\n')
+  w('          }\n        }\n      }\n    }\n')
+  w('    for (int j = 0; j < n_fields; ++j) { soda_hip_free(a[j]); soda_hip_free(b[j]); '
+    'soda_hip_free(c[j]); }\n')
+  w('    soda_hip_plan_destroy(plan);\n    soda_hip_module_unload(module);\n')
+  w('  };\n')
+  w('  std::vector<std::thread> threads;\n')
+  w('  for (int r = 0; r < ngpu; ++r) threads.emplace_back(worker, r);\n')
+  w('  for (auto& t : threads) t.join();\n')
+  w('  for (ncclComm_t comm : comms) if (comm) ncclCommDestroy(comm);\n')
+  w('  for (int rc : status) if (rc) return rc;\n')
+  w('  return 0;\n}\n#endif  // SODA_HIP_MULTI_GPU\n\n')
+
 
 def print_code(spec, kernels, out, lowered=None):
   """`spec`: the source program (golden loops, entry points); `lowered`: the
@@ -432,6 +588,9 @@ def print_code(spec, kernels, out, lowered=None):
   if len(ins) == 1 and len(outs) == 1:
     print_multi_gpu(spec, w, app, ins[0], outs[0], dim, max(
         [k['depth'] for k in kernels if k['kind'] == 'fused'] or [1]))
+  elif slabs_over_fields(spec):
+    print_multi_gpu_fields(spec, w, app, ins, outs, dim, max(
+        [k['depth'] for k in kernels if k['kind'] == 'fused'] or [1]))
 
   # ---- <app>_test --------------------------------------------------------------
   print_selfcheck(spec, out)
@@ -465,15 +624,17 @@ def print_code(spec, kernels, out, lowered=None):
                                  '+'.join('dims[%d]' % d for d in range(dim)))
     w('    %s_host[%s] = %s;\n' % (n, ' + '.join(
         '%c*stride%d' % (_COORD[d], d) for d in range(dim)), value))
-  if len(ins) == 1 and len(outs) == 1:
+  sharded = (len(ins) == 1 and len(outs) == 1) or slabs_over_fields(spec)
+  if sharded:
+    buffers = ''.join('&%s, ' % n for n in ins + outs)
     w('#ifdef SODA_HIP_MULTI_GPU\n')
-    w('  const int run_rc = getenv("SODA_GPUS") ? %s_multi_gpu(&%s, &%s, blob, iterate, '
-      'atoi(getenv("SODA_GPUS"))) : %s_iterate(&%s, &%s, blob, iterate);\n'
-      % (app, ins[0], outs[0], app, ins[0], outs[0]))
+    w('  const int run_rc = getenv("SODA_GPUS") ? %s_multi_gpu(%sblob, iterate, '
+      'atoi(getenv("SODA_GPUS"))) : %s_iterate(%sblob, iterate);\n'
+      % (app, buffers, app, buffers))
     w('#else\n')
   w('  const int run_rc = %s_iterate(%sblob, iterate);\n' % (
       app, ''.join('&%s, ' % n for n in ins + outs)))
-  if len(ins) == 1 and len(outs) == 1:
+  if sharded:
     w('#endif\n')
   w('  if (run_rc != 0) return run_rc < 0 ? -run_rc : run_rc;\n')
   w('  double threshold = 0.00001;\n')

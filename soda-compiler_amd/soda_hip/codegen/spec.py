@@ -293,6 +293,14 @@ def iteration_margins(spec, iterations):
   return out
 
 
+def iteration_field_margins(spec, iterations):
+  """[[(lo, hi) per output]] per iteration, as non-negative margins: after k+1 iterations
+  output j lives on [lo_d, N_d - hi_d) of its own (`iteration_margins` is the hull)."""
+  return [[(tuple(-v for v in boxes[name][0]), tuple(boxes[name][1]))
+           for name in spec['outputs']]
+          for boxes in iteration_boxes(spec, iterations)]
+
+
 def valid_cells(spec, dims, iterations):
   """Number of defined output cells summed over iterations 1..N (the "valid
   cell-updates" of SURVEY.md section 8d)."""

@@ -53,6 +53,13 @@ class KernelDesc(ctypes.Structure):
               ('stream_chunk', ctypes.c_int32), ('edge_slack', ctypes.c_int32)]
 
 
+class Args(ctypes.Structure):
+  """soda_hip_args: what a kernel receives by value (soda_hip_plan_schedule_fields)."""
+  _fields_ = [('tensor', ctypes.c_void_p * MAX_TENSORS),
+              ('dims', ctypes.c_int64 * MAX_DIMS), ('box_lo', ctypes.c_int64 * MAX_DIMS),
+              ('box_hi', ctypes.c_int64 * MAX_DIMS), ('param', ctypes.c_int64 * 4)]
+
+
 class Slab(ctypes.Structure):
   _fields_ = [('rank', ctypes.c_int32), ('world', ctypes.c_int32),
               ('reach_lo', ctypes.c_int32), ('reach_hi', ctypes.c_int32),
@@ -122,6 +129,16 @@ SIGNATURES = {
                                             ctypes.c_int, _VPP]),
     'soda_hip_plan_destroy': (ctypes.c_int, [_VP]),
     'soda_hip_plan_margins': (ctypes.c_int, [_VP, ctypes.c_int, _I32P, _I32P]),
+    'soda_hip_plan_field_margins': (ctypes.c_int, [_VP, ctypes.c_int, _I32P, _I32P]),
+    'soda_hip_plan_schedule_fields': (ctypes.c_int, [_VP, _I64P, ctypes.c_int, _I32P, _I32P,
+                                                     _I32P, ctypes.POINTER(ctypes.c_double),
+                                                     ctypes.POINTER(Args), ctypes.c_int,
+                                                     ctypes.POINTER(ctypes.c_int)]),
+    'soda_hip_sweep_fields': (ctypes.c_int, [_VP, _VPP, _VPP, _I64P, ctypes.c_int, _I32P,
+                                             _I32P, _VP]),
+    'soda_hip_run_slab_fields': (ctypes.c_int, [_VP, ctypes.POINTER(Slab), _VP, _VPP, _VPP,
+                                                _VPP, ctypes.c_int, _VP, _VPP,
+                                                ctypes.POINTER(ctypes.c_int)]),
     'soda_hip_plan_schedule': (ctypes.c_int, [_VP, _I64P, ctypes.c_int, _I32P, _I32P,
                                               _I32P, ctypes.POINTER(ctypes.c_double),
                                               ctypes.c_int,

@@ -21,6 +21,13 @@ Halo cells are recomputed instead of exchanged inside a super-step, which trades
 The sweep itself is an injected `engine` (the HIP program in production; the
 tests inject a CPU engine built on the oracle to exercise this logic under
 gloo without a GPU).
+
+Programs over several fields (as many outputs as inputs, output j feeding input j:
+wave2d, fdtd2d, maxwell3d ...) run the static cut in the serial order: a level is a LIST
+of arrays, one per field, `r_lo` / `r_hi` are the hull over the fields of one iteration's
+margins, one batched exchange per super-step carries every field's ghost rows, and
+`margins_of(k)` returns a (lo, hi) pair PER FIELD - each field's own box after k
+iterations (`fields_margins_of`) - which the global sides of every dimension carry.
 """
 import os
 import time
@@ -73,7 +80,13 @@ class SlabPlan:
   def valid_margins(self, done, margins_of):
     """valid_lo/valid_hi of the slab's input after `done` iterations, given
     `margins_of(k)` -> (lo, hi) tuples of the global margins after k iterations."""
-    lo, hi = margins_of(done)
+    m = margins_of(done)
+    if _per_field(m):
+      # a program over several fields: ([lo per field], [hi per field]), every field's own
+      # margins on the global sides of EVERY dimension, 0 on the sides with a neighbour
+      cut = [SlabPlan.valid_margins(self, done, lambda k, f=f: f) for f in m]
+      return [lo for lo, _ in cut], [hi for _, hi in cut]
+    lo, hi = m
     lo, hi = list(lo), list(hi)
     if self.has_lo:
       lo[-1] = 0
@@ -82,6 +95,21 @@ class SlabPlan:
     if self.has_hi:
       hi[-1] = 0
     return lo, hi
+
+
+def _per_field(margins):
+  """Whether margins_of(k) returned [(lo, hi) per field] rather than one (lo, hi)."""
+  return len(margins) > 0 and hasattr(margins[0][0], '__len__')
+
+
+def fields_margins_of(table):
+  """margins_of for run_slab on a program over several fields, from
+  `spec.iteration_field_margins(spec, iterate)`: [(lo, hi) per field] after k iterations."""
+  def margins_of(k):
+    if k == 0:
+      return [((0,) * len(lo), (0,) * len(hi)) for lo, hi in table[0]]
+    return table[k - 1]
+  return margins_of
 
 
 def _corrupt_received(rank, cut):
@@ -113,8 +141,10 @@ def _damage(rows):
 
 
 def exchange_ghosts(array, plan, dist, backend_ops=None):
-  """array: torch tensor of shape reversed(local_dims) (outer dim first).
-  Fills the ghost rows from the neighbours' own rows."""
+  """array: torch tensor of shape reversed(local_dims) (outer dim first), or the list of
+  them of a program over several fields: every field's rows travel in the ONE batch, a
+  send and a receive per field and neighbour, field by field (the rows of one field are
+  contiguous: nothing is packed).  Fills the ghost rows from the neighbours' own rows."""
   if plan.world == 1:
     return
   ops = []
@@ -124,20 +154,21 @@ def exchange_ghosts(array, plan, dist, backend_ops=None):
   # bytes are bytes: unsigned element types travel as the signed type of the same
   # width (RCCL has no uint16 / uint32 / uint64)
   signed = {'torch.uint16': 'int16', 'torch.uint32': 'int32', 'torch.uint64': 'int64'}
-  if str(array.dtype) in signed:
-    import torch
-    array = array.view(getattr(torch, signed[str(array.dtype)]))
 
   def add(op, rows, peer):     # a one-sided window has nothing to ship one way:
     if rows.shape[0] > 0:      # both sides skip that (empty) message
       ops.append(dist.P2POp(op, rows, peer))
-  if plan.has_lo:
-    # lower neighbour: it needs our first send_down rows, we need its last rows
-    add(dist.isend, array[first_own:first_own + plan.send_down], plan.rank - 1)
-    add(dist.irecv, array[0:g_lo], plan.rank - 1)
-  if plan.has_hi:
-    add(dist.isend, array[last_own - plan.send_up:last_own], plan.rank + 1)
-    add(dist.irecv, array[last_own:last_own + g_hi], plan.rank + 1)
+  for array in (list(array) if isinstance(array, (list, tuple)) else [array]):
+    if str(array.dtype) in signed:
+      import torch
+      array = array.view(getattr(torch, signed[str(array.dtype)]))
+    if plan.has_lo:
+      # lower neighbour: it needs our first send_down rows, we need its last rows
+      add(dist.isend, array[first_own:first_own + plan.send_down], plan.rank - 1)
+      add(dist.irecv, array[0:g_lo], plan.rank - 1)
+    if plan.has_hi:
+      add(dist.isend, array[last_own - plan.send_up:last_own], plan.rank + 1)
+      add(dist.irecv, array[last_own:last_own + g_hi], plan.rank + 1)
   if ops:
     for req in dist.batch_isend_irecv(ops):
       req.wait()
@@ -206,9 +237,15 @@ def run_slab(engine, plan, arrays, iterate, margins_of, dist, ghosts_ready=False
   overlapping schedule (StreamSchedule on GPUs) makes every super-step but the
   last produce the rows its neighbours need FIRST, as two thin band sweeps, hands
   them to the exchange of the next super-step on a side stream, and sweeps the
-  interior meanwhile."""
+  interior meanwhile.
+
+  A program over several fields: A, B and C are lists of arrays, one per field, and
+  margins_of(k) returns a (lo, hi) pair per field (fields_margins_of); serial order only."""
   a, b, c = arrays
   schedule = schedule or SerialSchedule()
+  if isinstance(a, (list, tuple)) and schedule.overlapped:
+    raise ValueError('bands-first order: single-array programs only; programs over '
+                     'several fields run the serial order')
   src, done, exchanges = a, 0, 0
   dst_cycle = [b, c]
   k = 0
@@ -439,6 +476,8 @@ def run_recut(engine, plan, arrays, margins_of, dist, ghosts_ready=False, schedu
   declared valid (the rows there were produced or received): its output box is exactly
   the rank's rows of the output level, on every rank alike - the first and last rank read
   from the edge of the valid rows, which is where their sub-arrays start."""
+  if isinstance(arrays[0], (list, tuple)):
+    raise ValueError('static cut only for programs over several fields')
   a, b, c = arrays
   schedule = schedule or SerialSchedule()
   src, exchanges = a, 0
@@ -557,21 +596,25 @@ class HipEngine:
     """rows = (r0, r1): sweep only the sub-array of those rows of the outermost
     dimension (a contiguous piece of memory: the same call on offset pointers).
     final_only: dst is written by the sweep's last launch only
-    (soda_hip_plan_set_out_final_only)."""
+    (soda_hip_plan_set_out_final_only).
+    src, dst: one array, or one per field (then valid_lo / valid_hi hold a margin per
+    field as well: soda_hip_sweep_fields)."""
     if final_only != self.final_only:
       self.program.set_out_final_only(final_only)
       self.final_only = final_only
     stream = self.torch.cuda.current_stream().cuda_stream
     dims = list(local_dims)
-    sp, dp = src.data_ptr(), dst.data_ptr()
+    srcs = list(src) if isinstance(src, (list, tuple)) else [src]
+    dsts = list(dst) if isinstance(dst, (list, tuple)) else [dst]
+    sp, dp = [t.data_ptr() for t in srcs], [t.data_ptr() for t in dsts]
     if rows is not None:
-      row_bytes = src.element_size()
-      for n in dims[:-1]:
-        row_bytes *= n
-      sp, dp = sp + rows[0] * row_bytes, dp + rows[0] * row_bytes
+      for j, t in enumerate(srcs):
+        row_bytes = t.element_size()
+        for n in dims[:-1]:
+          row_bytes *= n
+        sp[j], dp[j] = sp[j] + rows[0] * row_bytes, dp[j] + rows[0] * row_bytes
       dims[-1] = rows[1] - rows[0]
-    self.program.sweep([sp], [dp], dims, iterations, valid_lo, valid_hi,
-                       stream=stream)
+    self.program.sweep(sp, dp, dims, iterations, valid_lo, valid_hi, stream=stream)
 
 
 class StreamSchedule:

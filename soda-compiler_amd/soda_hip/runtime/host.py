@@ -252,6 +252,44 @@ class Program:
     d = self.spec['dim']
     return tuple(lo[:d]), tuple(hi[:d])
 
+  def field_margins(self, iterations):
+    """[(lo, hi)] per output after `iterations` iterations of a fresh run
+    (soda_hip_plan_field_margins); `margins` is the hull of these."""
+    n, d = len(self.spec['outputs']), self.spec['dim']
+    lo = (ctypes.c_int32 * (4 * n))()
+    hi = (ctypes.c_int32 * (4 * n))()
+    capi.check(capi.lib().soda_hip_plan_field_margins(self.handle, iterations, lo, hi))
+    return [(tuple(lo[4 * j:4 * j + d]), tuple(hi[4 * j:4 * j + d])) for j in range(n)]
+
+  def _margins(self, valid):
+    """(per_field, ctypes array or None) of a valid_lo / valid_hi argument: one margin
+    for all inputs (a flat sequence of numbers) or one per input (a sequence of them)."""
+    if valid is None:
+      return False, None
+    valid = list(valid)
+    if valid and not hasattr(valid[0], '__len__'):
+      return False, (ctypes.c_int32 * 4)(*(valid + [0] * (4 - len(valid))))
+    n = len(self.spec['inputs'])
+    if len(valid) != n:
+      raise ValueError('%d valid regions for %d inputs' % (len(valid), n))
+    flat = []
+    for v in valid:
+      flat += list(v) + [0] * (4 - len(v))
+    return True, (ctypes.c_int32 * (4 * n))(*flat)
+
+  def _valid_regions(self, valid_lo, valid_hi):
+    """(per_field, lo, hi) for the C entries; a flat margin beside a per-input one is
+    repeated for every input."""
+    f_lo, lo = self._margins(valid_lo)
+    f_hi, hi = self._margins(valid_hi)
+    if f_lo != f_hi:
+      n = len(self.spec['inputs'])
+      if not f_lo:
+        lo = self._margins([list(lo or [0] * 4)[:4]] * n)[1]
+      else:
+        hi = self._margins([list(hi or [0] * 4)[:4]] * n)[1]
+    return f_lo or f_hi, lo, hi
+
   @staticmethod
   def _ptr_array(ptrs):
     return (ctypes.c_void_p * len(ptrs))(*ptrs)
@@ -262,15 +300,13 @@ class Program:
 
   def sweep(self, in_ptrs, out_ptrs, dims, iterate, valid_lo=None, valid_hi=None,
             stream=None):
-    """Asynchronous device sweep on raw device pointers."""
-    vlo = vhi = None
-    if valid_lo is not None:
-      vlo = (ctypes.c_int32 * 4)(*(list(valid_lo) + [0] * (4 - len(valid_lo))))
-    if valid_hi is not None:
-      vhi = (ctypes.c_int32 * 4)(*(list(valid_hi) + [0] * (4 - len(valid_hi))))
-    capi.check(capi.lib().soda_hip_sweep(
-        self.handle, self._ptr_array(in_ptrs), self._ptr_array(out_ptrs),
-        self._dims(dims), iterate, vlo, vhi, stream))
+    """Asynchronous device sweep on raw device pointers.  valid_lo / valid_hi: one
+    margin for all inputs ((lo_0, lo_1, ..), soda_hip_sweep) or one per input
+    ([(lo_0, ..), ..] in input order, soda_hip_sweep_fields)."""
+    per_field, vlo, vhi = self._valid_regions(valid_lo, valid_hi)
+    entry = capi.lib().soda_hip_sweep_fields if per_field else capi.lib().soda_hip_sweep
+    capi.check(entry(self.handle, self._ptr_array(in_ptrs), self._ptr_array(out_ptrs),
+                     self._dims(dims), iterate, vlo, vhi, stream))
 
   def tune(self, in_ptrs, out_ptrs, dims, iterate, valid_lo=None, valid_hi=None,
            stream=None):
@@ -318,6 +354,28 @@ class Program:
         self.handle, self._dims(dims), iterate, vlo, vhi, idx, est, n.value,
         ctypes.byref(n)))
     return [(self.kernels[idx[i]], est[i]) for i in range(n.value)]
+
+  def schedule_fields(self, dims, iterate, valid_lo=None, valid_hi=None):
+    """The launches of `sweep` with a valid region per input, boxes included:
+    [dict(kernel=table entry, est_us, lo, hi, param)] (soda_hip_plan_schedule_fields)."""
+    n_in = len(self.spec['inputs'])
+    zero = [[0] * 4] * n_in
+    _, vlo, vhi = self._valid_regions(zero if valid_lo is None else valid_lo,
+                                      zero if valid_hi is None else valid_hi)
+    n = ctypes.c_int()
+    capi.check(capi.lib().soda_hip_plan_schedule_fields(
+        self.handle, self._dims(dims), iterate, vlo, vhi, None, None, None, 0,
+        ctypes.byref(n)))
+    idx = (ctypes.c_int32 * max(1, n.value))()
+    est = (ctypes.c_double * max(1, n.value))()
+    args = (capi.Args * max(1, n.value))()
+    capi.check(capi.lib().soda_hip_plan_schedule_fields(
+        self.handle, self._dims(dims), iterate, vlo, vhi, idx, est, args, n.value,
+        ctypes.byref(n)))
+    d = self.spec['dim']
+    return [dict(kernel=self.kernels[idx[i]], est_us=est[i], lo=list(args[i].box_lo[:d]),
+                 hi=list(args[i].box_hi[:d]), param=list(args[i].param))
+            for i in range(n.value)]
 
   def sweep_timed(self, in_ptrs, out_ptrs, dims, iterate, warmup=1, repeats=1,
                   stream=None):
