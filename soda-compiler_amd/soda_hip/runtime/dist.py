@@ -102,14 +102,30 @@ def _per_field(margins):
   return len(margins) > 0 and hasattr(margins[0][0], '__len__')
 
 
-def fields_margins_of(table):
-  """margins_of for run_slab on a program over several fields, from
-  `spec.iteration_field_margins(spec, iterate)`: [(lo, hi) per field] after k iterations."""
+def table_margins_of(table):
+  """margins_of for run_slab / run_recut from a table whose entry k - 1 holds the margins
+  after k iterations - `spec.iteration_margins(spec, iterate)`: (lo, hi), or for a program
+  over several fields `spec.iteration_field_margins(spec, iterate)`: [(lo, hi) per field];
+  k = 0: zeros of the same shape."""
+  def zeros(m):
+    return type(m)(zeros(v) for v in m) if hasattr(m, '__len__') else 0
+
   def margins_of(k):
-    if k == 0:
-      return [((0,) * len(lo), (0,) * len(hi)) for lo, hi in table[0]]
-    return table[k - 1]
+    return zeros(table[0]) if k == 0 else table[k - 1]
   return margins_of
+
+
+fields_margins_of = table_margins_of      # (the name the drivers of several fields use)
+
+
+def _wire(array):
+  """Bytes are bytes: unsigned element types travel as the signed type of the same width
+  (RCCL has no uint16 / uint32 / uint64)."""
+  signed = {'torch.uint16': 'int16', 'torch.uint32': 'int32', 'torch.uint64': 'int64'}
+  if str(array.dtype) in signed:
+    import torch
+    return array.view(getattr(torch, signed[str(array.dtype)]))
+  return array
 
 
 def _corrupt_received(rank, cut):
@@ -151,17 +167,12 @@ def exchange_ghosts(array, plan, dist, backend_ops=None):
   g_lo, g_hi, own = plan.ghost_lo, plan.ghost_hi, plan.own
   first_own = g_lo
   last_own = g_lo + own
-  # bytes are bytes: unsigned element types travel as the signed type of the same
-  # width (RCCL has no uint16 / uint32 / uint64)
-  signed = {'torch.uint16': 'int16', 'torch.uint32': 'int32', 'torch.uint64': 'int64'}
 
   def add(op, rows, peer):     # a one-sided window has nothing to ship one way:
     if rows.shape[0] > 0:      # both sides skip that (empty) message
       ops.append(dist.P2POp(op, rows, peer))
   for array in (list(array) if isinstance(array, (list, tuple)) else [array]):
-    if str(array.dtype) in signed:
-      import torch
-      array = array.view(getattr(torch, signed[str(array.dtype)]))
+    array = _wire(array)
     if plan.has_lo:
       # lower neighbour: it needs our first send_down rows, we need its last rows
       add(dist.isend, array[first_own:first_own + plan.send_down], plan.rank - 1)
@@ -445,10 +456,7 @@ def exchange_rows(array, plan, s, dist):
   of RecutPlan.messages(s)."""
   if plan.world == 1:
     return
-  signed = {'torch.uint16': 'int16', 'torch.uint32': 'int32', 'torch.uint64': 'int64'}
-  if str(array.dtype) in signed:
-    import torch
-    array = array.view(getattr(torch, signed[str(array.dtype)]))
+  array = _wire(array)
   sends, recvs = plan.messages(s)
   ops = []
   for peer, rows in sends:
@@ -774,11 +782,7 @@ def multi_rank_check(torch, dist, program, spec, make_input, margin_table_of, ra
   plan = make_plan(static, cdims, rank, world, r_lo, r_hi, exchange, cit)
   engine = HipEngine(program, torch)
   table = margin_table_of(cit)
-
-  def margins_of(k):
-    if k == 0:
-      return (0,) * spec['dim'], (0,) * spec['dim']
-    return table[k - 1]
+  margins_of = table_margins_of(table)
   own = torch.from_numpy(make_input(spec, cdims, rows=(plan.start, plan.stop))[0]).to(dev)
   shape = tuple(reversed(plan.local_dims))
   a, b, c = (torch.zeros(shape, dtype=own.dtype, device=dev) for _ in range(3))
@@ -791,8 +795,6 @@ def multi_rank_check(torch, dist, program, spec, make_input, margin_table_of, ra
   torch.cuda.synchronize()
   (first, last), offset = result_rows(plan)
   mine = result[offset:offset + (last - first)].contiguous()
-  signed = {'torch.uint16': torch.int16, 'torch.uint32': torch.int32}
-  wire = (lambda t: t.view(signed[str(t.dtype)]) if str(t.dtype) in signed else t)
   differing = 0
   if rank == 0:
     whole_in = torch.from_numpy(make_input(spec, cdims)[0]).to(dev)
@@ -805,7 +807,7 @@ def multi_rank_check(torch, dist, program, spec, make_input, margin_table_of, ra
     for q in range(1, world):
       (qa, qb), _ = result_rows(make_plan(static, cdims, q, world, r_lo, r_hi, exchange, cit))
       if qb > qa:
-        ops.append(dist.P2POp(dist.irecv, wire(got)[qa:qb], q))
+        ops.append(dist.P2POp(dist.irecv, _wire(got)[qa:qb], q))
     if ops:
       if backend != 'nccl':
         torch.cuda.synchronize()
@@ -820,7 +822,7 @@ def multi_rank_check(torch, dist, program, spec, make_input, margin_table_of, ra
   elif last > first:
     if backend != 'nccl':
       torch.cuda.synchronize()
-    for req in dist.batch_isend_irecv([dist.P2POp(dist.isend, wire(mine), 0)]):
+    for req in dist.batch_isend_irecv([dist.P2POp(dist.isend, _wire(mine), 0)]):
       req.wait()
     torch.cuda.synchronize()
   verdict = torch.tensor([differing], dtype=torch.int64,
@@ -904,12 +906,7 @@ def bench_main(args, open_program, make_input, per_iteration_updates,
     full_shape = tuple(reversed(dims[:-1] + [rows]))
     storage = [torch.zeros(full_shape, dtype=tdt, device=dev) for _ in range(3)]
     engine = HipEngine(program, torch)
-    margin_table = specmod.iteration_margins(spec, args.iterate)
-
-    def margins_of(k):
-      if k == 0:
-        return (0,) * spec['dim'], (0,) * spec['dim']
-      return margin_table[k - 1]
+    margins_of = table_margins_of(specmod.iteration_margins(spec, args.iterate))
 
     def setup(exchange, overlapped, static_cut=None):
       """(plan, [a, b, c], order, step) of one candidate: a holds the own rows at
