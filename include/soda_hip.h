@@ -143,10 +143,15 @@ typedef struct soda_hip_kernel {
   int32_t block[3]; /* workgroup shape */
   int32_t tile[SODA_HIP_MAX_DIMS]; /* output cells one workgroup produces; for a
                                       streaming kernel the outer-dimension entry
-                                      is only the default chunk length */
+                                      is only the default chunk length.  A FUSED
+                                      kernel of a 1-D program has no outer
+                                      dimension to stream along: tile[0] is all
+                                      a workgroup produces, in one go */
   int32_t fill_rows; /* streaming kernels: extra outer-dimension rows a workgroup
                         walks through before its first output row (pipeline
-                        fill + halo); 0 = not a streaming kernel */
+                        fill + halo); 0 = not a streaming kernel (per-stage
+                        kernels, and the fused kernels of 1-D programs, whose
+                        step_valu / step_bytes are then per workgroup per LAUNCH) */
   int32_t origin_align; /* > 1: the kernel starts its dimension-0 tiles at box_lo[0]
                            rounded down to a multiple of this (cache-line aligned
                            strips) and tile[0] is exact; 0/1: tiles start at

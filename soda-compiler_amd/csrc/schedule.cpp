@@ -342,6 +342,20 @@ int64_t choose_stream_chunk(const Planner* plan, int k, const soda_hip_args& arg
   return best;
 }
 
+// Fused kernel of a 1-D program (kernel_stream1d.py): no streamed dimension, a workgroup
+// does its whole tile in one go - step_valu and step_bytes are per workgroup per launch.
+// The price is the launch constant plus, per chip-full of workgroups, the larger of a
+// workgroup's VALU time and its bytes at the chip's streaming rate (step_seconds).
+void price_segments(const Planner* plan, int k, const soda_hip_args& args, Launch* out) {
+  const double resident = std::max(1, plan->resident_blocks[k]);
+  const double blocks = out->grid[0];
+  const double rounds = std::ceil(blocks / resident);
+  out->rounds = (long long)rounds;
+  out->resident = (long long)resident;
+  out->est_us = kModelLaunchUs +
+                rounds * step_seconds(plan, k, blocks, footprint_of(plan, args), resident) * 1e6;
+}
+
 // the first and the last tile of a row store the columns the alignment left over
 // (include/soda_hip.h: edge_slack): tiles start up to `slack` columns inside the box.
 // Returns the tiles along x; *origin = the column they start at.
@@ -539,6 +553,7 @@ int make_launch(const Planner* plan, int k, const soda_hip_args& launch_args,
     int rc = fold_rows(plan, desc, args, out);
     if (rc) return rc;
   }
+  if (dim == 1 && desc.kind == SODA_HIP_KERNEL_FUSED) price_segments(plan, k, args, out);
   if (desc.xcd_tiles < 0 && dim == 3) return place_runs(desc, edge_origin, out);
   if (desc.xcd_tiles && dim == 3) return place_super_tiles(plan, k, out);
   return 0;
@@ -595,11 +610,14 @@ bool plans_fused(const Planner* plan, const std::vector<int>& fused, const int64
   if (fused.empty() || plan->kernels[fused.back()].depth != 1) return false;
   if (plan->max_depth < 0) return false;  // force per-stage kernels
   if (plan->max_depth == 0 && !plan->tuning &&
-      takes_output_extras(plan, plan->kernels[fused.back()])) {
+      (takes_output_extras(plan, plan->kernels[fused.back()]) || plan->prog.dim == 1)) {
     // The fused kernels over several fields have not been timed on an MI355X yet
     // (profiles/r07_fields.txt, r07_fields3d.txt), so no depth of theirs has earned its place in the default
     // schedule: they run where the caller asks for them, with a depth limit
     // (soda_hip_plan_set_max_depth > 0) or a split (soda_hip_plan_set_split, _tune).
+    // The same holds for the fused kernels of 1-D programs (kernel_stream1d.py;
+    // profiles/r10_stream1d.txt): admitting a depth of theirs to the default schedule is a
+    // change of its own.
     return plan->tuned_split.find(split_key(plan, dims, iterate)) != plan->tuned_split.end();
   }
   return true;

@@ -11,6 +11,7 @@ The unit holds
   * the fused kernels of the program's family, at the depths selected below:
       multi-field 2-D   kernel_fields2d
       multi-field 3-D   kernel_fields3d
+      single-array 1-D  kernel_stream1d (segments of one wavefront, no streaming)
       single-array 2-D  kernel_stream2d (one strip per wavefront) or, deep,
                         kernel_stream2d_wp (wave-pipelined)
       3-D, depth 1-2    kernel_stream3d (one tile per wavefront)
@@ -31,8 +32,9 @@ import subprocess
 import tempfile
 
 from .. import __version__
-from . import (kernel_common, kernel_fields2d, kernel_fields3d, kernel_stage, kernel_stream2d,
-               kernel_stream2d_wp, kernel_stream3d, kernel_stream3d_blk, kernel_stream3d_wp)
+from . import (kernel_common, kernel_fields2d, kernel_fields3d, kernel_stage, kernel_stream1d,
+               kernel_stream2d, kernel_stream2d_wp, kernel_stream3d, kernel_stream3d_blk,
+               kernel_stream3d_wp)
 from . import spec as specmod
 
 DEFAULT_MAX_DEPTH = 12
@@ -131,6 +133,12 @@ FIELDS_OPTIONS = ('skip_fill', 'vgpr_budget', 'max_period', 'waves_per_eu')
 # programs go in tiles that keep any cells
 FIELDS3D_DEPTHS = (1, 2)
 FIELDS3D_OPTIONS = ('rows', 'vgpr_budget', 'max_period', 'waves_per_eu')
+# depths of the 1-D form (kernel_stream1d), capped by the program's `iterate`: those of
+# fused_depths.  A level is one vector per lane, so no depth is refused for registers; a
+# depth that profiles/r10_stream1d.txt shows not to beat the per-stage schedule leaves
+# this list
+STREAM1D_DEPTHS = (1, 2, 4, 8, 12)
+STREAM1D_OPTIONS = ('segs',)
 
 # generator options of the fused 2-D forms that `generate` passes through:
 # those both forms understand, and those only the wave-pipelined form has
@@ -322,7 +330,14 @@ def annotate_cost(entry, spec):
   weight = max(1, arithmetic_weight(spec))
   waves = entry['block'][0] // kernel_stream2d.LANES
   n_in, n_out = len(spec['inputs']), len(spec['outputs'])
-  if spec['dim'] == 2 and 'groups' in entry:      # wave-pipelined: one strip(-pair)
+  if spec['dim'] == 1:
+    # no streamed dimension: the figures are per workgroup per LAUNCH - every level of
+    # every segment of its wavefronts, and the cells it loads and stores
+    lane_cells = entry['segs'] * entry['cols']
+    valu = waves * entry['depth'] * weight * lane_cells * 2
+    cells_in = waves * kernel_stream2d.LANES * lane_cells
+    cells_out = entry['tile'][0]
+  elif spec['dim'] == 2 and 'groups' in entry:    # wave-pipelined: one strip(-pair)
     lane_cells = entry['cols'] * (2 if entry.get('pairs') else 1)
     valu = entry['depth'] * weight * lane_cells * 2 + WP_STEP_FIXED_CYCLES
     cells_in, cells_out = kernel_stream2d.LANES * lane_cells, entry['tile'][0]
@@ -372,17 +387,18 @@ def prefixed_options(options, prefix, emit):
 # Which of generate()'s `**fused_options` a kernel form receives: the one place that says so.
 # Tools pass one option set across programs of different families, so what a form does not
 # receive is dropped in silence, while a name that reaches an emit() which does not take it
-# is a TypeError.  fields2d, fields3d and stream2d_wp receive the names listed for them; stream2d and
+# is a TypeError.  fields2d, fields3d, stream1d and stream2d_wp receive the names listed for them; stream2d and
 # stream3d every name but those held back for the other forms (a name nobody knows therefore
 # ends in their emit()); stream3d_blk and stream3d_wp the `blk_` / `wp_` names, checked
 # against the emit() by prefixed_options.
 FORM_OPTIONS = dict(
     fields2d=lambda k: k in FIELDS_OPTIONS,
     fields3d=lambda k: k in FIELDS3D_OPTIONS,
-    stream2d=lambda k: k not in WP_ONLY_OPTIONS and k != 'nt',
+    stream1d=lambda k: k in STREAM1D_OPTIONS,
+    stream2d=lambda k: k not in WP_ONLY_OPTIONS + STREAM1D_OPTIONS and k != 'nt',
     stream2d_wp=lambda k: k in SHARED_2D_OPTIONS + WP_ONLY_OPTIONS,
     stream3d=lambda k: not k.startswith(('wp_', 'blk_')) and
-    k not in ('deep3d', 'deep3d_from', 'nontemporal'))
+    k not in ('deep3d', 'deep3d_from', 'nontemporal') + STREAM1D_OPTIONS)
 PREFIXED_FORMS = dict(stream3d_blk=('blk_', kernel_stream3d_blk.emit),
                       stream3d_wp=('wp_', kernel_stream3d_wp.emit))
 
@@ -468,6 +484,26 @@ def fields3d_kernels(req, notes):
     found, error = first_fusable(spec, depth, [
         (kernel_fields3d.emit, dict(options, rows=rows, cols=lane_cols))
         for rows, lane_cols in shapes])
+    if found is None:
+      notes.append('depth %d not fused: %s' % (depth, error))
+      if depth == 1:      # the scheduler needs depth 1: without it, per-stage kernels
+        return
+      continue
+    yield found
+
+
+def stream1d_kernels(req, notes):
+  """1-D programs: kernel_stream1d at each depth."""
+  spec = req.spec
+  if spec['dim'] != 1:
+    return
+  wanted = [d for d in req.default_depths if d in STREAM1D_DEPTHS]
+  if req.depths is not None:
+    wanted = sorted(set([1] + [d for d in req.depths if req.chain or d == 1]))
+  for depth in wanted:
+    found, error = first_fusable(spec, depth, [
+        (kernel_stream1d.emit, dict(form_options('stream1d', req.options),
+                                    cols=req.strip['cols']))])
     if found is None:
       notes.append('depth %d not fused: %s' % (depth, error))
       if depth == 1:      # the scheduler needs depth 1: without it, per-stage kernels
@@ -734,8 +770,8 @@ def deep3d_kernels(req, notes):
 
 # the kernel families in the order their kernels enter the table; each yields the
 # (text, entry) of the kernels it selects for this request and appends to `notes`
-FAMILIES = (fields2d_kernels, fields3d_kernels, stream2d_kernels, stream3d_kernels,
-            deep3d_kernels)
+FAMILIES = (fields2d_kernels, fields3d_kernels, stream1d_kernels, stream2d_kernels,
+            stream3d_kernels, deep3d_kernels)
 
 
 def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
