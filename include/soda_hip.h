@@ -270,7 +270,15 @@ typedef struct soda_hip_args {
                        each 0..255: output j is stored on
                          [box_lo[d] - lo_d, box_hi[d] + hi_d), d = 0, 1, 2.
                        That is room for 3 outputs; programs with more keep their
-                       per-stage kernels. */
+                       per-stage kernels.
+                       Fused 1-D kernels of such programs: two extras per output,
+                       16 bits each, four outputs to a word (output j in word
+                       1 + j / 4, bits 16 (j % 4) up):
+                         lo0 | hi0 << 8,
+                       each 0..255: output j is stored on
+                         [box_lo[0] - lo0, box_hi[0] + hi0).
+                       Six outputs at most (param[1] and the low half of param[2]);
+                       programs with more keep their per-stage kernels. */
 } soda_hip_args;
 
 /* ---- plan -------------------------------------------------------------------

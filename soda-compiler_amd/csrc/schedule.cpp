@@ -231,20 +231,22 @@ namespace {
 // Fused kernels of programs with several outputs (kernel_fields2d.py, kernel_fields3d.py)
 // store output j on a box of its own: the launch's box - the intersection of the outputs'
 // boxes - widened by the extras of soda_hip_args.param[1..3] (include/soda_hip.h): 2-D four
-// extras of 8 bits per output, two outputs to a word; 3-D six, one output to a word.
+// extras of 8 bits per output, two outputs to a word; 3-D six, one output to a word; 1-D
+// (kernel_fields1d.py) two, four outputs to a word.
 constexpr int kMaxExtra = 255;
 
-int max_extra_outputs(int dim) { return dim == 2 ? 6 : 3; }
+int max_extra_outputs(int dim) { return dim == 3 ? 3 : 6; }
 
 bool takes_output_extras(const Planner* plan, const soda_hip_kernel& desc) {
-  return desc.kind == SODA_HIP_KERNEL_FUSED && (plan->prog.dim == 2 || plan->prog.dim == 3) &&
+  return desc.kind == SODA_HIP_KERNEL_FUSED && plan->prog.dim >= 1 && plan->prog.dim <= 3 &&
          plan->prog.n_outputs > 1;
 }
 
 // extras of output j: {lo of dimension 0 .. dim - 1, hi of dimension 0 .. dim - 1}
 void unpack_extras(int dim, const soda_hip_args& a, int j, int64_t* ex) {
-  const uint64_t word = dim == 2 ? (uint64_t)a.param[1 + j / 2] >> (32 * (j % 2))
-                                 : (uint64_t)a.param[1 + j];
+  const uint64_t word = dim == 1   ? (uint64_t)a.param[1 + j / 4] >> (16 * (j % 4))
+                        : dim == 2 ? (uint64_t)a.param[1 + j / 2] >> (32 * (j % 2))
+                                   : (uint64_t)a.param[1 + j];
   for (int i = 0; i < 2 * dim; ++i) ex[i] = (word >> (8 * i)) & 0xff;
 }
 
@@ -783,7 +785,8 @@ int pack_output_extras(const Planner* plan, const Growth* g, const soda_hip_kern
     if (rc) return rc;
     uint64_t word = 0;
     for (int i = 0; i < 2 * dim; ++i) word |= (uint64_t)ex[i] << (8 * i);
-    if (dim == 2) a->param[1 + j / 2] |= (int64_t)(word << (32 * (j % 2)));
+    if (dim == 1) a->param[1 + j / 4] |= (int64_t)(word << (16 * (j % 4)));
+    else if (dim == 2) a->param[1 + j / 2] |= (int64_t)(word << (32 * (j % 2)));
     else a->param[1 + j] = (int64_t)word;
   }
   return 0;

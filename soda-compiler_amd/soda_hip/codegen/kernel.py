@@ -11,6 +11,7 @@ The unit holds
   * the fused kernels of the program's family, at the depths selected below:
       multi-field 2-D   kernel_fields2d
       multi-field 3-D   kernel_fields3d
+      multi-field 1-D   kernel_fields1d (kernel_stream1d's segments over N fields)
       single-array 1-D  kernel_stream1d (segments of one wavefront, no streaming)
       single-array 2-D  kernel_stream2d (one strip per wavefront) or, deep,
                         kernel_stream2d_wp (wave-pipelined)
@@ -32,9 +33,9 @@ import subprocess
 import tempfile
 
 from .. import __version__
-from . import (kernel_common, kernel_fields2d, kernel_fields3d, kernel_stage, kernel_stream1d,
-               kernel_stream2d, kernel_stream2d_wp, kernel_stream3d, kernel_stream3d_blk,
-               kernel_stream3d_wp)
+from . import (kernel_common, kernel_fields1d, kernel_fields2d, kernel_fields3d, kernel_stage,
+               kernel_stream1d, kernel_stream2d, kernel_stream2d_wp, kernel_stream3d,
+               kernel_stream3d_blk, kernel_stream3d_wp)
 from . import spec as specmod
 
 DEFAULT_MAX_DEPTH = 12
@@ -139,6 +140,8 @@ FIELDS3D_OPTIONS = ('rows', 'vgpr_budget', 'max_period', 'waves_per_eu')
 # this list
 STREAM1D_DEPTHS = (1, 2, 4, 8, 12)
 STREAM1D_OPTIONS = ('segs',)
+# the 1-D form over several fields (kernel_fields1d) takes the same depths and options
+FIELDS1D_OPTIONS = STREAM1D_OPTIONS
 
 # generator options of the fused 2-D forms that `generate` passes through:
 # those both forms understand, and those only the wave-pipelined form has
@@ -387,13 +390,15 @@ def prefixed_options(options, prefix, emit):
 # Which of generate()'s `**fused_options` a kernel form receives: the one place that says so.
 # Tools pass one option set across programs of different families, so what a form does not
 # receive is dropped in silence, while a name that reaches an emit() which does not take it
-# is a TypeError.  fields2d, fields3d, stream1d and stream2d_wp receive the names listed for them; stream2d and
+# is a TypeError.  fields1d, fields2d, fields3d, stream1d and stream2d_wp receive the names
+# listed for them; stream2d and
 # stream3d every name but those held back for the other forms (a name nobody knows therefore
 # ends in their emit()); stream3d_blk and stream3d_wp the `blk_` / `wp_` names, checked
 # against the emit() by prefixed_options.
 FORM_OPTIONS = dict(
     fields2d=lambda k: k in FIELDS_OPTIONS,
     fields3d=lambda k: k in FIELDS3D_OPTIONS,
+    fields1d=lambda k: k in FIELDS1D_OPTIONS,
     stream1d=lambda k: k in STREAM1D_OPTIONS,
     stream2d=lambda k: k not in WP_ONLY_OPTIONS + STREAM1D_OPTIONS and k != 'nt',
     stream2d_wp=lambda k: k in SHARED_2D_OPTIONS + WP_ONLY_OPTIONS,
@@ -440,6 +445,9 @@ class Request:
     elif spec['dim'] == 3:
       self.default_depths = [d for d in (1, 2) if d <= max(1, spec['iterate'])] \
           if self.single_array else [1]
+    elif spec['dim'] == 1 and kernel_stream2d.multi_field(spec):
+      self.default_depths = [d for d in STREAM1D_DEPTHS
+                             if d <= self.max_depth and d <= max(1, spec['iterate'])]
     else:
       self.default_depths = list(fused_depths(spec, self.max_depth))
     # the program is an iteration chain the fused forms can deepen (anything else gets
@@ -492,10 +500,30 @@ def fields3d_kernels(req, notes):
     yield found
 
 
-def stream1d_kernels(req, notes):
-  """1-D programs: kernel_stream1d at each depth."""
+def fields1d_kernels(req, notes):
+  """Multi-field 1-D programs: kernel_fields1d at each depth."""
   spec = req.spec
-  if spec['dim'] != 1:
+  if spec['dim'] != 1 or not kernel_stream2d.multi_field(spec):
+    return
+  wanted = req.default_depths
+  if req.depths is not None:
+    wanted = sorted(set([1] + list(req.depths)))
+  for depth in wanted:
+    found, error = first_fusable(spec, depth, [
+        (kernel_fields1d.emit, dict(form_options('fields1d', req.options),
+                                    cols=req.strip['cols']))])
+    if found is None:
+      notes.append('depth %d not fused: %s' % (depth, error))
+      if depth == 1:      # the scheduler needs depth 1: without it, per-stage kernels
+        return
+      continue
+    yield found
+
+
+def stream1d_kernels(req, notes):
+  """1-D programs over one array: kernel_stream1d at each depth."""
+  spec = req.spec
+  if spec['dim'] != 1 or kernel_stream2d.multi_field(spec):
     return
   wanted = [d for d in req.default_depths if d in STREAM1D_DEPTHS]
   if req.depths is not None:
@@ -770,8 +798,8 @@ def deep3d_kernels(req, notes):
 
 # the kernel families in the order their kernels enter the table; each yields the
 # (text, entry) of the kernels it selects for this request and appends to `notes`
-FAMILIES = (fields2d_kernels, fields3d_kernels, stream1d_kernels, stream2d_kernels,
-            stream3d_kernels, deep3d_kernels)
+FAMILIES = (fields2d_kernels, fields3d_kernels, fields1d_kernels, stream1d_kernels,
+            stream2d_kernels, stream3d_kernels, deep3d_kernels)
 
 
 def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,

@@ -91,6 +91,24 @@ def geometry(spec, depth, cols):
               origin_align=cols)
 
 
+def emit_vector_load(emit_line, function, vec, T, C, elem):
+  """The vector type `vec` of C cells of T, aligned to the element only, and the load of
+  one lane's vector through it: whole when the wavefront is INTERIOR, else cell by cell
+  with cells outside the array reading as 0.  (kernel_fields1d prints one per element
+  type.)"""
+  emit_line('typedef %s %s __attribute__((ext_vector_type(%d), aligned(%d)));'
+            % (T, vec, C, elem))
+  emit_line('template <bool INTERIOR>')
+  emit_line('DEV %s %s(const %s* __restrict__ g, const i64 x, const i64 W) {'
+            % (vec, function, T))
+  emit_line('  if (INTERIOR) return *(const %s*)(g + x);' % vec)
+  emit_line('  %s v;' % vec)
+  for c in range(C):
+    emit_line('  v[%d] = (x + %d >= 0 && x + %d < W) ? g[x + %d] : (%s)0;' % (c, c, c, c, T))
+  emit_line('  return v;')
+  emit_line('}')
+
+
 def emit(spec, depth, cols=None, segs=DEFAULT_SEGS):
   """Returns (text, kernel table entry) for one fused depth of a 1-D program."""
   levels = build_levels(spec, depth)
@@ -127,17 +145,7 @@ def emit(spec, depth, cols=None, segs=DEFAULT_SEGS):
   emit_line('// segment = %d cells (%d out + halo %d/%d), workgroup = %d cells out'
             % (LANES * C, geo['w_out'], geo['halo_lo'], geo['halo_hi'],
                segs * stride))
-  emit_line('typedef %s %s __attribute__((ext_vector_type(%d), aligned(%d)));'
-            % (T, vec, C, elem))
-  emit_line('template <bool INTERIOR>')
-  emit_line('DEV %s %s_load(const %s* __restrict__ g, const i64 x, const i64 W) {'
-            % (vec, name, T))
-  emit_line('  if (INTERIOR) return *(const %s*)(g + x);' % vec)
-  emit_line('  %s v;' % vec)
-  for c in range(C):
-    emit_line('  v[%d] = (x + %d >= 0 && x + %d < W) ? g[x + %d] : (%s)0;' % (c, c, c, c, T))
-  emit_line('  return v;')
-  emit_line('}')
+  emit_vector_load(emit_line, '%s_load' % name, vec, T, C, elem)
   # one segment: every level from the loaded cells, then the store.  Every lane computes
   # every level (the DPP operands are read with all lanes active); only the store is
   # conditional

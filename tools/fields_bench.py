@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Multi-field programs, fused against per-stage, on one GPU: wave2d and fdtd2d at
 8192 x 8192 x 100 iterations or, with `--apps 3d` (wave3d and maxwell3d), at
-384 x 384 x 384 x 20, under bench.py's protocol (warm-up sweeps, then the median
+384 x 384 x 384 x 20 or, with `--apps 1d` (wave1d and fdtd1d), at 2^27 cells x 96, under
+bench.py's protocol (warm-up sweeps, then the median
 of event-timed sweeps; sweeps are repeated until the timed region is long enough for
 steady clocks).
 
@@ -20,10 +21,12 @@ A depth SHIPS if its median time per iteration is below the per-stage one by mor
 the run-to-run spread: the larger of the two schedules' (max - min) over the timed sweeps.
 Registers, occupancy and scratch per kernel are read from the code object's metadata; for
 the 3-D kernels the tile and the fraction of it that survives the halo come from the table.
+For the 1-D kernels the derived HBM bytes per cell-update of every depth stand next to the
+register figures; `--static` prints those two and times nothing (no GPU needed).
 Prints one JSON line per program and writes the whole table to the file given with --out.
 
-    python tools/fields_bench.py [--apps 2d | 3d | APP ...] [--size W H [D]] [--iterate N]
-                                 [--sweeps K] [--out FILE]
+    python tools/fields_bench.py [--apps 1d | 2d | 3d | APP ...] [--size W [H [D]]]
+                                 [--iterate N] [--sweeps K] [--static] [--out FILE]
 """
 import argparse
 import json
@@ -40,7 +43,9 @@ for p in (ROOT, os.path.join(ROOT, 'soda-compiler_amd'), os.path.join(ROOT, 'tes
 
 
 READELF = '/opt/rocm/lib/llvm/bin/llvm-readelf'
-DEFAULTS = {'2d': ('wave2d', 'fdtd2d'), '3d': ('wave3d', 'maxwell3d')}
+DEFAULTS = {'1d': ('wave1d', 'fdtd1d'), '2d': ('wave2d', 'fdtd2d'), '3d': ('wave3d', 'maxwell3d')}
+SIZES = {1: [1 << 27], 2: [8192, 8192], 3: [384, 384, 384]}
+ITERATE = {1: 96, 2: 100, 3: 20}
 
 
 def isa_figures(blob, names):
@@ -59,29 +64,60 @@ def isa_figures(blob, names):
   return out
 
 
+def traffic_lines(spec, kernels):
+  """Derived, not measured: HBM bytes per cell-update of the per-stage schedule (every stage
+  reads each tensor it names once and writes its result) and of every fused 1-D depth (a
+  segment loads 64 * cols cells of every field for the w_out it stores, once per `depth`
+  updates)."""
+  from soda_hip.codegen import spec as specmod
+  lowered = specmod.inline_pointwise(spec)
+  types = specmod.tensor_c_types(lowered)
+  staged = sum(specmod.ELEM_SIZE[types[t]] for stage in lowered['stages']
+               for t in sorted({name for name, _ in stage['loads']}) + [stage['name']])
+  lines = ['  derived HBM bytes per cell-update: per-stage %d' % staged]
+  for k in sorted((k for k in kernels if k['kind'] == 'fused' and k.get('fields') and
+                   k['fill_rows'] == 0), key=lambda k: k['depth']):
+    elem = specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
+    per = (len(spec['inputs']) * 64.0 * k['cols'] / k['w_out'] + len(spec['outputs'])) * \
+        elem / k['depth']
+    lines.append('  %-22s %5.2f B per cell-update (segment %d cells, %d stored, %d segments '
+                 'per wavefront)' % (k['name'], per, 64 * k['cols'], k['w_out'], k['segs']))
+  return lines
+
+
+def isa_lines(figures, depth_of):
+  return ['  %-22s %3d VGPRs, %d waves per SIMD, %3d SGPRs, scratch %d B, spills '
+          '%d VGPR / %d SGPR' % (
+              kname, f['vgpr_count'], min(8, 512 // (-(-f['vgpr_count'] // 8) * 8)),
+              f['sgpr_count'], f['private_segment_fixed_size'],
+              f['vgpr_spill_count'], f['sgpr_spill_count'])
+          for kname, f in sorted(figures.items(), key=lambda kf: depth_of[kf[0]])]
+
+
 def main():
   ap = argparse.ArgumentParser(description=__doc__,
                                formatter_class=argparse.RawDescriptionHelpFormatter)
   ap.add_argument('--apps', nargs='+', default=['2d'],
-                  help="'2d' = wave2d fdtd2d, '3d' = wave3d maxwell3d, or sample names of "
+                  help="'1d' = wave1d fdtd1d, '2d' = wave2d fdtd2d, '3d' = wave3d maxwell3d, or sample names of "
                   'one dimensionality')
   ap.add_argument('--size', nargs='+', type=int, default=None,
-                  help='default 8192 8192, for 3-D programs 384 384 384')
-  ap.add_argument('--iterate', type=int, default=None, help='default 100, for 3-D programs 20')
+                  help='default 8192 8192, for 3-D programs 384 384 384, for 1-D ones 2^27')
+  ap.add_argument('--iterate', type=int, default=None,
+                  help='default 100, for 3-D programs 20, for 1-D ones 96')
+  ap.add_argument('--static', action='store_true',
+                  help='the static figures only (registers, derived traffic): no GPU')
   ap.add_argument('--sweeps', type=int, default=7, help='timed sweeps per schedule (>= 3)')
   ap.add_argument('--warmup', type=int, default=3)
   ap.add_argument('--out', default=None)
   args = ap.parse_args()
-  import numpy as np
   import __graft_entry__ as entry
   from soda_hip import frontend
   from soda_hip.codegen import spec as specmod
-  from soda_hip.runtime import host
   assert args.sweeps >= 3
   args.apps = [a for name in args.apps for a in DEFAULTS.get(name, (name,))]
   dim = specmod.spec_from_stencil(frontend.load(entry.sample_path(args.apps[0])))['dim']
-  args.size = args.size or ([8192, 8192] if dim == 2 else [384, 384, 384])
-  args.iterate = args.iterate or (100 if dim == 2 else 20)
+  args.size = args.size or SIZES[dim]
+  args.iterate = args.iterate or ITERATE[dim]
   assert len(args.size) == dim, '--size needs %d extents' % dim
   dims = tuple(args.size)
   shape = tuple(reversed(dims))
@@ -105,6 +141,16 @@ def main():
     spec = specmod.spec_from_stencil(frontend.load(entry.sample_path(app)))
     assert spec['dim'] == dim, '%s is not a %d-D program' % (app, dim)
     blob = entry.blob_path(app)
+    if args.static:
+      from soda_hip.codegen import kernel
+      table = kernel.generate(spec)[1]
+      depth_of = {k['name']: k['depth'] for k in table if k['kind'] == 'fused'}
+      lines.append('%s: NOT YET MEASURED (static figures only)' % app)
+      lines += isa_lines(isa_figures(blob, depth_of), depth_of)
+      lines += traffic_lines(spec, table) if dim == 1 else []
+      continue
+    import numpy as np
+    from soda_hip.runtime import host
     prog = host.open_program(blob=blob, spec=spec)
     rng = np.random.default_rng(7)
     cells = int(np.prod(shape))
@@ -173,13 +219,9 @@ def main():
     fused_names = {k['name']: k['depth'] for k in prog.kernels if k['kind'] == 'fused'}
     figures = isa_figures(blob, fused_names)
     result['isa'] = figures
-    for kname in sorted(figures, key=fused_names.get):
-      f = figures[kname]
-      lines.append('  %-22s %3d VGPRs, %d waves per SIMD, %3d SGPRs, scratch %d B, spills '
-                   '%d VGPR / %d SGPR' % (
-                       kname, f['vgpr_count'], min(8, 512 // (-(-f['vgpr_count'] // 8) * 8)),
-                       f['sgpr_count'], f['private_segment_fixed_size'],
-                       f['vgpr_spill_count'], f['sgpr_spill_count']))
+    lines += isa_lines(figures, fused_names)
+    if dim == 1:
+      lines += traffic_lines(spec, prog.kernels)
     for k in sorted((k for k in prog.kernels if k['kind'] == 'fused' and 'rows' in k),
                     key=lambda k: k['depth']):
       lines.append('  %-22s tile %d x %d per wavefront, %d x %d stored: %.2f of it kept' % (
