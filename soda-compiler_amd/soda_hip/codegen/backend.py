@@ -15,6 +15,10 @@ This module has the same two, with `--hip-*` flags where the Xilinx one has
                       text (cf. --xocl-hw-xo, which runs the Vivado tools)
   --hip [DIR]         all of the above under default names (cf. --xocl)
 
+  --hip-fuse-outputs  one-pass 2-D / 3-D programs with several outputs that do not feed
+                      the inputs pairwise get one fused depth-1 kernel storing every
+                      output (kernel.generate: fuse_outputs); goes into every product
+
 `-` writes to stdout.  `stencil` may be this project's `frontend.Stencil` or the
 reference's `soda.core.Stencil` (INTEGRATION.md).
 """
@@ -54,6 +58,10 @@ def add_arguments(parser):
                       'by burst width)')
   parser.add_argument('--hip-chunk-rows', type=int, dest='hip_chunk_rows',
                       metavar='ROWS', help='outer-dimension rows per workgroup')
+  parser.add_argument('--hip-fuse-outputs', action='store_true', dest='hip_fuse_outputs',
+                      help='one fused depth-1 kernel for a one-pass 2-D / 3-D program '
+                      'with several outputs (launched under a depth limit of 1: '
+                      'soda_hip_plan_set_max_depth)')
 
 
 def to_spec(stencil):
@@ -118,7 +126,8 @@ def print_code(stencil, args):
   if files['kernel'] or files['blob'] or files['host_cpp']:
     text, table = kernel.generate(
         spec, max_depth=max_depth, cols=getattr(args, 'hip_cols', None),
-        chunk_rows=getattr(args, 'hip_chunk_rows', None))
+        chunk_rows=getattr(args, 'hip_chunk_rows', None),
+        fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)))
   if files['kernel']:
     _logger.info('generate HIP kernel code as %s', files['kernel'])
     f, close = _open(files['kernel'])
@@ -128,7 +137,7 @@ def print_code(stencil, args):
   if files['host']:
     _logger.info('generate host shim as %s', files['host'])
     f, close = _open(files['host'])
-    host_shim.print_code(spec, f)
+    host_shim.print_code(spec, f, fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)))
     if close:
       f.close()
   if files['header']:
@@ -140,7 +149,8 @@ def print_code(stencil, args):
   if files['host_cpp']:
     _logger.info('generate C++ host as %s', files['host_cpp'])
     f, close = _open(files['host_cpp'])
-    host_cpp.print_code(spec, table, f, lowered=specmod.inline_pointwise(spec))
+    host_cpp.print_code(spec, table, f, lowered=specmod.inline_pointwise(spec),
+                        fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)))
     if close:
       f.close()
   if files['blob']:

@@ -11,6 +11,8 @@ The unit holds
   * the fused kernels of the program's family, at the depths selected below:
       multi-field 2-D   kernel_fields2d
       multi-field 3-D   kernel_fields3d
+      one pass, several outputs, 2-D / 3-D (kernel_stream2d.rectangular): the same two
+                        forms at depth 1, only with `fuse_outputs=True`
       multi-field 1-D   kernel_fields1d (kernel_stream1d's segments over N fields)
       single-array 1-D  kernel_stream1d (segments of one wavefront, no streaming)
       single-array 2-D  kernel_stream2d (one strip per wavefront) or, deep,
@@ -134,6 +136,16 @@ FIELDS_OPTIONS = ('skip_fill', 'vgpr_budget', 'max_period', 'waves_per_eu')
 # programs go in tiles that keep any cells
 FIELDS3D_DEPTHS = (1, 2)
 FIELDS3D_OPTIONS = ('rows', 'vgpr_budget', 'max_period', 'waves_per_eu')
+# Rectangular 3-D programs (one pass, several outputs; `fuse_outputs`): rows of a tile x
+# inputs at most.  Every input adds a plane pointer and a row of loads per tile row to what
+# the plane loop keeps in scalar registers: mix3d (three inputs, two outputs) in 16-row tiles
+# compiles with one SGPR pair parked in a VGPR in its array-edge path, in 12-row tiles with
+# 96 SGPRs and none; grad3d (one input, three outputs) takes 16 rows with 104 and none.
+# The smallest tile has 8 rows, so a rectangular 3-D program has at most FOUR inputs; with
+# more it keeps its per-stage kernels and a note (2-D has no such cap).  The figure rests on
+# these two samples: a program that spills under it shows in the compiler's resource report
+# (tests/test_rect_codegen.py reads it for every sample), not at run time.
+RECT3D_INPUT_ROWS = 36
 # depths of the 1-D form (kernel_stream1d), capped by the program's `iterate`: those of
 # fused_depths.  A level is one vector per lane, so no depth is refused for registers; a
 # depth that profiles/r10_stream1d.txt shows not to beat the per-stage schedule leaves
@@ -391,7 +403,9 @@ def prefixed_options(options, prefix, emit):
 # Tools pass one option set across programs of different families, so what a form does not
 # receive is dropped in silence, while a name that reaches an emit() which does not take it
 # is a TypeError.  fields1d, fields2d, fields3d, stream1d and stream2d_wp receive the names
-# listed for them; stream2d and
+# listed for them (rectangular programs under `fuse_outputs` go through fields2d / fields3d
+# and receive what those receive; `fuse_outputs` itself is an argument of generate(), not a
+# form option); stream2d and
 # stream3d every name but those held back for the other forms (a name nobody knows therefore
 # ends in their emit()); stream3d_blk and stream3d_wp the `blk_` / `wp_` names, checked
 # against the emit() by prefixed_options.
@@ -430,8 +444,18 @@ class Request:
   """What generate() was asked for, normalised once; every family function receives it."""
 
   def __init__(self, spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
-               options):
+               options, fuse_outputs=False):
     self.spec, self.depths, self.options = spec, depths, options
+    # one-pass programs with several outputs get the fields forms at depth 1 (opt-in:
+    # profiles/r12_rect.txt); such a program is in nobody else's class
+    self.rect = bool(fuse_outputs) and kernel_stream2d.rectangular(spec)
+    if fuse_outputs and not self.rect and len(spec['outputs']) >= 2 and \
+        spec['dim'] in (2, 3) and not kernel_stream2d.multi_field(spec):
+      self.rect_refusal = ('outputs not fused: iterate %d over %d input(s) and %d output(s) '
+                           'that do not feed each other pairwise' % (
+                               spec['iterate'], len(spec['inputs']), len(spec['outputs'])))
+    else:
+      self.rect_refusal = None
     self.max_depth = DEFAULT_MAX_DEPTH if max_depth is None else max_depth
     self.cols, self.prefetch = cols, prefetch       # as given: a form may have its own default
     # columns per lane, rows per chunk and rows in flight of the 2-D strips
@@ -456,14 +480,17 @@ class Request:
 
 
 def fields2d_kernels(req, notes):
-  """Multi-field 2-D programs: kernel_fields2d at each depth."""
+  """Multi-field 2-D programs: kernel_fields2d at each depth; rectangular ones, when
+  generate() was asked to fuse their outputs, at depth 1."""
   spec = req.spec
-  if spec['dim'] != 2 or not kernel_stream2d.multi_field(spec):
+  if spec['dim'] == 2 and req.rect_refusal:
+    notes.append(req.rect_refusal)
+  if spec['dim'] != 2 or not (kernel_stream2d.multi_field(spec) or req.rect):
     return
   wanted = req.default_depths
   if req.depths is not None:
     wanted = sorted(set([1] + list(req.depths)))
-  for depth in wanted:
+  for depth in [1] if req.rect else wanted:
     found, error = first_fusable(spec, depth, [
         (kernel_fields2d.emit, dict(req.strip, **form_options('fields2d', req.options)))])
     if found is None:
@@ -476,19 +503,28 @@ def fields2d_kernels(req, notes):
 
 def fields3d_kernels(req, notes):
   """Multi-field 3-D programs: kernel_fields3d at each depth, in the tile shape that keeps
-  most of the tile among those the register budget takes."""
+  most of the tile among those the register budget takes; rectangular ones, when generate()
+  was asked to fuse their outputs, at depth 1."""
   spec = req.spec
-  if spec['dim'] != 3 or not kernel_stream2d.multi_field(spec):
+  if spec['dim'] == 3 and req.rect_refusal:
+    notes.append(req.rect_refusal)
+  if spec['dim'] != 3 or not (kernel_stream2d.multi_field(spec) or req.rect):
     return
   wanted = req.default_depths
   if req.depths is not None:
     wanted = sorted(set([1] + list(req.depths)))
-  for depth in wanted:
+  for depth in [1] if req.rect else wanted:
     options = form_options('fields3d', req.options)
     shapes = [s for s in kernel_fields3d.shapes_by_kept_fraction(spec, depth)
               if not req.cols or s[1] == req.cols]
+    if req.rect:
+      shapes = [s for s in shapes if s[0] * len(spec['inputs']) <= RECT3D_INPUT_ROWS]
     if 'rows' in options:
       shapes = [(options.pop('rows'), req.cols or 2)]
+    if not shapes:
+      notes.append('depth %d not fused: %d inputs, 3-D tiles take %d rows x inputs' % (
+          depth, len(spec['inputs']), RECT3D_INPUT_ROWS))
+      return
     found, error = first_fusable(spec, depth, [
         (kernel_fields3d.emit, dict(options, rows=rows, cols=lane_cols))
         for rows, lane_cols in shapes])
@@ -650,7 +686,7 @@ def stream2d_piped(req, depth, strip, notes):
 def stream2d_kernels(req, notes):
   """Single-array 2-D programs: per depth the wave-pipelined kernel, else the single-wave."""
   spec = req.spec
-  if spec['dim'] != 2 or kernel_stream2d.multi_field(spec):
+  if spec['dim'] != 2 or kernel_stream2d.multi_field(spec) or req.rect:
     return
   for depth in stream2d_depths(req):
     strip = dict(req.strip)
@@ -680,7 +716,7 @@ def stream2d_kernels(req, notes):
 def stream3d_kernels(req, notes):
   """3-D programs, depths 1 and 2: one tile per wavefront (kernel_stream3d)."""
   spec, cols = req.spec, req.cols
-  if spec['dim'] != 3 or kernel_stream2d.multi_field(spec):
+  if spec['dim'] != 3 or kernel_stream2d.multi_field(spec) or req.rect:
     return
   wanted = req.default_depths
   if req.depths is not None:
@@ -804,9 +840,14 @@ FAMILIES = (fields2d_kernels, fields3d_kernels, fields1d_kernels, stream1d_kerne
 
 def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
              fused=True, depths=None, inline=True, wave_groups=None,
-             **fused_options):
+             fuse_outputs=False, **fused_options):
   """Returns (kernel text, kernel table).  `depths` overrides the default set
-  of fused depths (depth 1 is always included: the scheduler needs it)."""
+  of fused depths (depth 1 is always included: the scheduler needs it).
+  `fuse_outputs`: a one-pass 2-D / 3-D program with several outputs that is not
+  multi_field (kernel_stream2d.rectangular) gets ONE fused depth-1 kernel that stores
+  every output (kernel_fields2d / kernel_fields3d) besides its per-stage kernels; the
+  run-time launches it under a depth limit of 1 (soda_hip_plan_set_max_depth).  Without
+  it such a program keeps per-stage kernels only."""
   # kernels are generated from the LOWERED program (pointwise-only locals folded
   # into their readers); the blob is still identified by the source program
   source = spec
@@ -822,7 +863,7 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   parts.append(text)
   notes = []
   req = Request(spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
-                fused_options)
+                fused_options, fuse_outputs=fuse_outputs)
   for family in FAMILIES if fused else ():
     for ftext, entry in family(req, notes):
       parts.append(ftext)

@@ -23,6 +23,11 @@ form adds:
     clamped into the array on both sides, columns outside it read as 0.  Such values
     reach only cells outside every output's box (boxes are the composed windows).
 
+The same form serves, at depth 1, one-pass programs with several outputs that feed nothing
+back (kernel_stream2d.rectangular: `#inputs != #outputs`, or outputs of other types than the
+inputs): the pairing of output j with input j only matters between iterations.  Every
+tensor is then of one element width, of any type at that width.
+
 One guarded row loop serves every depth (no branch-free steady-state copy as in the
 single-field form): the per-output store ranges would double its variants.  What the loop
 keeps per output is small on purpose - the rows it stores as a range of 32-bit step
@@ -34,7 +39,8 @@ from . import spec as specmod
 from .kernel_common import builtin_type, cell_assignment, tensor_index
 from .kernel_stream2d import (LANES, WAVES_PER_BLOCK, NotFusable, build_pipeline,
                               estimated_vgprs, geometry, kernel_name, lane_operand,
-                              multi_field, rotation_period, set_first_steps, slot)
+                              multi_field, rectangular, rotation_period, set_first_steps,
+                              slot)
 
 # soda_hip_args.param[1..3]: four 8-bit extras per output, 32 bits each
 MAX_OUTPUTS = 6
@@ -67,8 +73,10 @@ def pack_extras(extras):
 
 def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
          vgpr_budget=244, waves_per_eu=0, skip_fill=1):
-  """Returns (text, kernel table entry) for one fused depth of a multi-field program."""
-  if not multi_field(spec):
+  """Returns (text, kernel table entry) for one fused depth of a multi-field program, or
+  for depth 1 of a rectangular one (kernel_stream2d.rectangular)."""
+  rect = depth == 1 and rectangular(spec)
+  if not multi_field(spec) and not rect:
     raise NotFusable('fields2d handles programs whose outputs feed their inputs pairwise')
   if len(spec['outputs']) > MAX_OUTPUTS:
     raise NotFusable('%d outputs: the launch arguments carry the boxes of %d'
@@ -77,6 +85,10 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
   elem = specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
   if any(specmod.ELEM_SIZE[t['c_type']] != elem for t in spec['inputs']):
     raise NotFusable('fields of different widths')
+  if rect and any(specmod.ELEM_SIZE[t] != elem for t in specmod.tensor_c_types(spec).values()):
+    # (outputs and locals need not be of an input's type, but of its width: one lane
+    # holds the same columns of every tensor)
+    raise NotFusable('tensors of different widths')
   if cols is None:
     cols = max(1, 16 // elem)
   C = cols
@@ -113,7 +125,8 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
     emit_line('//   %-18s %4d %4d%s' % (inst.ident, inst.lag, inst.keep,
                                         '  -> HBM' if inst.final else ''))
   vec = {}
-  for c_type in sorted({t['c_type'] for t in spec['inputs']}):
+  # (a rectangular program may store an output of a type no input has)
+  for c_type in sorted({t['c_type'] for t in spec['inputs']} | {i.c_type for i in finals}):
     vec[c_type] = 'vec_%s_%s' % (name, c_type)
     emit_line('typedef %s %s __attribute__((ext_vector_type(%d), aligned(%d)));'
               % (builtin_type(c_type), vec[c_type], C, elem))

@@ -22,12 +22,15 @@ that window over all fields.  No LDS, no barrier.  What this form adds:
   * nothing about the union is assumed beyond its lying inside the array: planes and
     rows are clamped into the array on both sides, columns outside it read as 0.  Such
     values reach only cells outside every output's box (boxes are the composed windows).
+
+At depth 1 the form also takes one-pass programs with several outputs that feed nothing back
+(kernel_stream2d.rectangular), as kernel_fields2d does.
 """
 
 from . import spec as specmod
 from .kernel_common import builtin_type, cell_assignment, tensor_index
 from .kernel_stream2d import (LANES, WAVES_PER_BLOCK, NotFusable, multi_field,
-                              rotation_period, slot)
+                              rectangular, rotation_period, slot)
 from .kernel_stream3d import kernel_name, pipeline
 
 # soda_hip_args.param[1..3]: six 8-bit extras per output, one word each
@@ -82,8 +85,10 @@ def shapes_by_kept_fraction(spec, depth, shapes=TILE_SHAPES):
 
 def emit(spec, depth, cols=2, rows=16, chunk_planes=64, prefetch=0, max_period=12,
          vgpr_budget=250, waves_per_eu=0):
-  """Returns (text, kernel table entry) for one fused depth of a 3-D multi-field program."""
-  if spec['dim'] != 3 or not multi_field(spec):
+  """Returns (text, kernel table entry) for one fused depth of a 3-D multi-field program, or
+  for depth 1 of a rectangular one (kernel_stream2d.rectangular)."""
+  rect = depth == 1 and rectangular(spec)
+  if spec['dim'] != 3 or not (multi_field(spec) or rect):
     raise NotFusable('fields3d handles 3-D programs whose outputs feed their inputs pairwise')
   if len(spec['outputs']) > MAX_OUTPUTS:
     raise NotFusable('%d outputs: the launch arguments carry the boxes of %d'
@@ -133,7 +138,8 @@ def emit(spec, depth, cols=2, rows=16, chunk_planes=64, prefetch=0, max_period=1
     line('//   %-18s lag %2d keep %2d%s' % (inst.ident, inst.lag, inst.keep,
                                            '  -> HBM' if inst.final else ''))
   vec = {}
-  for c_type in sorted({t['c_type'] for t in spec['inputs']}):
+  # (a rectangular program may store an output of a type no input has)
+  for c_type in sorted({t['c_type'] for t in spec['inputs']} | {i.c_type for i in finals}):
     vec[c_type] = 'vec_%s_%s' % (name, c_type)
     line('typedef %s %s __attribute__((ext_vector_type(%d), aligned(%d)));'
          % (builtin_type(c_type), vec[c_type], C, elem))
@@ -276,7 +282,14 @@ def emit(spec, depth, cols=2, rows=16, chunk_planes=64, prefetch=0, max_period=1
       if inst.final:
         j = out_of[id(inst)]
         line('      {  // store plane head+%d-%d of %s' % (u, inst.lag, inst.tensor))
-        line('        const i64 z = head + %d;' % (u - inst.lag))
+        if rect:
+          # (with outputs and inputs in unequal numbers the compiler turns the address of
+          # every stored row of every output into an induction variable of the plane loop,
+          # a pair of scalar registers each, which the file does not have: the plane
+          # number passes through the empty asm and the addresses are computed per plane)
+          line('        i64 z = head + %d; %s_opaque_s(z);' % (u - inst.lag, name))
+        else:
+          line('        const i64 z = head + %d;' % (u - inst.lag))
         line('        if (n + %d >= n_lo%d && n + %d < n_hi%d) {' % (u, j, u, j))
         line('          %s* q = g_out%d + z * plane + row_base + x;' % (ctype, j))
         line('          int r_lo = r_lo%d, r_hi = r_hi%d; %s_opaque_s(r_lo); %s_opaque_s(r_hi);'

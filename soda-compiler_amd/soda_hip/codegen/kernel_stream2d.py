@@ -62,13 +62,23 @@ def multi_field(spec):
       t['c_type'] == types[o] for t, o in zip(spec['inputs'], spec['outputs']))
 
 
+def rectangular(spec):
+  """One-pass programs with several outputs that are not multi_field: `iterate: 1`, two or
+  more outputs, 2-D or 3-D, and either `#inputs != #outputs` or an output j that is not of
+  input j's type (a gradient, a colour split, tests/samples/extra/outchain.soda).  Nothing
+  feeds anything back, so the fields forms take them at depth 1 as they are."""
+  return spec['iterate'] == 1 and len(spec['outputs']) >= 2 and spec['dim'] in (2, 3) and \
+      not multi_field(spec)
+
+
 def build_pipeline(spec, depth, prefetch, fields=False):
   """fields: the caller stores every output (kernel_fields2d) - multi_field programs
-  are taken, and the last iteration's instance of EVERY output is marked final."""
+  are taken, rectangular ones at depth 1, and the last iteration's instance of EVERY
+  output is marked final."""
   if spec['dim'] != 2:
     raise NotFusable('stream2d handles 2-D programs')
   ins = [t['name'] for t in spec['inputs']]
-  if not (fields and multi_field(spec)):
+  if not (fields and (multi_field(spec) or (rectangular(spec) and depth == 1))):
     if len(spec['outputs']) != 1:
       raise NotFusable('stream2d handles single-output programs')
     if depth > 1 and len(ins) != 1:
