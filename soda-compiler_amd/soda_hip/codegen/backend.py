@@ -18,6 +18,9 @@ This module has the same two, with `--hip-*` flags where the Xilinx one has
   --hip-fuse-outputs  one-pass 2-D / 3-D programs with several outputs that do not feed
                       the inputs pairwise get one fused depth-1 kernel storing every
                       output (kernel.generate: fuse_outputs); goes into every product
+  --hip-lds-planes    3-D programs of one stage whose window is wider than a lane's columns
+                      (stars of radius 3 and up) get the LDS-plane kernel <app>_fused_k1l
+                      (kernel.generate: lds_planes); goes into every product
 
 `-` writes to stdout.  `stencil` may be this project's `frontend.Stencil` or the
 reference's `soda.core.Stencil` (INTEGRATION.md).
@@ -62,6 +65,10 @@ def add_arguments(parser):
                       help='one fused depth-1 kernel for a one-pass 2-D / 3-D program '
                       'with several outputs (launched under a depth limit of 1: '
                       'soda_hip_plan_set_max_depth)')
+  parser.add_argument('--hip-lds-planes', action='store_true', dest='hip_lds_planes',
+                      help='one fused depth-1 kernel with the in-plane neighbours in LDS '
+                      'for a one-stage 3-D program no other fused form takes (high-order '
+                      'stars); it runs in the default schedule')
 
 
 def to_spec(stencil):
@@ -104,6 +111,7 @@ def print_code(stencil, args):
   spec = to_spec(stencil)
   warn_ignored_overrides(args)
   max_depth = getattr(args, 'hip_max_depth', None)
+  lds_planes = bool(getattr(args, 'hip_lds_planes', False))
   files = dict(kernel=getattr(args, 'hip_kernel_file', None),
                host=getattr(args, 'hip_host_file', None),
                header=getattr(args, 'hip_header_file', None),
@@ -127,7 +135,7 @@ def print_code(stencil, args):
     text, table = kernel.generate(
         spec, max_depth=max_depth, cols=getattr(args, 'hip_cols', None),
         chunk_rows=getattr(args, 'hip_chunk_rows', None),
-        fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)))
+        fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)), lds_planes=lds_planes)
   if files['kernel']:
     _logger.info('generate HIP kernel code as %s', files['kernel'])
     f, close = _open(files['kernel'])
@@ -137,7 +145,8 @@ def print_code(stencil, args):
   if files['host']:
     _logger.info('generate host shim as %s', files['host'])
     f, close = _open(files['host'])
-    host_shim.print_code(spec, f, fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)))
+    host_shim.print_code(spec, f, fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)),
+                         lds_planes=lds_planes)
     if close:
       f.close()
   if files['header']:

@@ -19,7 +19,10 @@ The unit holds
                         kernel_stream2d_wp (wave-pipelined)
       3-D, depth 1-2    kernel_stream3d (one tile per wavefront)
       3-D chains        kernel_stream3d_blk (block form) and / or
-                        kernel_stream3d_wp (wave-pipelined);
+                        kernel_stream3d_wp (wave-pipelined)
+      3-D, one stage, windows wider than a lane's columns: kernel_stream3d_lds (the
+                        in-plane neighbours from an LDS plane), only with `lds_planes=True`
+                        and only where no other form made a depth-1 kernel;
   * `soda_hip_meta`, JSON describing the program and the kernel table, which
     libsoda_hip.so reads back from the loaded blob.
 
@@ -37,7 +40,7 @@ import tempfile
 from .. import __version__
 from . import (kernel_common, kernel_fields1d, kernel_fields2d, kernel_fields3d, kernel_stage,
                kernel_stream1d, kernel_stream2d, kernel_stream2d_wp, kernel_stream3d,
-               kernel_stream3d_blk, kernel_stream3d_wp)
+               kernel_stream3d_blk, kernel_stream3d_lds, kernel_stream3d_wp)
 from . import spec as specmod
 
 DEFAULT_MAX_DEPTH = 12
@@ -154,6 +157,9 @@ STREAM1D_DEPTHS = (1, 2, 4, 8, 12)
 STREAM1D_OPTIONS = ('segs',)
 # the 1-D form over several fields (kernel_fields1d) takes the same depths and options
 FIELDS1D_OPTIONS = STREAM1D_OPTIONS
+# the LDS-plane 3-D form (kernel_stream3d_lds; `lds_planes`): `lds_shape` = (wavefronts, rows
+# per lane, lanes per tile row) instead of the first shape that fits
+LDS3D_OPTIONS = ('lds_shape',)
 
 # generator options of the fused 2-D forms that `generate` passes through:
 # those both forms understand, and those only the wave-pipelined form has
@@ -360,6 +366,12 @@ def annotate_cost(entry, spec):
     valu = waves * entry['depth'] * weight * entry['cols'] * 2
     cells_in = waves * kernel_stream2d.LANES * entry['cols']
     cells_out = entry['tile'][0]
+  elif 'lds_planes' in entry:                     # 3-D, in-plane neighbours from LDS:
+    # every wavefront computes RW x C cells per lane; the planes in LDS come with their
+    # halo ring, the other inputs tile for tile (kernel_stream3d_lds: loaded_cells)
+    valu = waves * weight * entry['rows'] * entry['cols'] * 2
+    cells_in, cells_out = entry['loaded_cells'], entry['tile'][0] * entry['tile'][1]
+    n_in = 1
   elif 'groups' in entry:                         # 3-D, one level per wavefront
     lane_cells = entry['rows'] * entry['cols']
     valu = entry['depth'] * weight * lane_cells * 2 + WP_STEP_FIXED_CYCLES
@@ -417,7 +429,8 @@ FORM_OPTIONS = dict(
     stream2d=lambda k: k not in WP_ONLY_OPTIONS + STREAM1D_OPTIONS and k != 'nt',
     stream2d_wp=lambda k: k in SHARED_2D_OPTIONS + WP_ONLY_OPTIONS,
     stream3d=lambda k: not k.startswith(('wp_', 'blk_')) and
-    k not in ('deep3d', 'deep3d_from', 'nontemporal') + STREAM1D_OPTIONS)
+    k not in ('deep3d', 'deep3d_from', 'nontemporal') + STREAM1D_OPTIONS + LDS3D_OPTIONS,
+    stream3d_lds=lambda k: k in LDS3D_OPTIONS)
 PREFIXED_FORMS = dict(stream3d_blk=('blk_', kernel_stream3d_blk.emit),
                       stream3d_wp=('wp_', kernel_stream3d_wp.emit))
 
@@ -444,8 +457,11 @@ class Request:
   """What generate() was asked for, normalised once; every family function receives it."""
 
   def __init__(self, spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
-               options, fuse_outputs=False):
+               options, fuse_outputs=False, lds_planes=False):
     self.spec, self.depths, self.options = spec, depths, options
+    # the LDS-plane 3-D form was asked for (opt-in), and the table entries made so far: it
+    # is emitted only where they hold no fused depth-1 kernel
+    self.lds_planes, self.made = bool(lds_planes), []
     # one-pass programs with several outputs get the fields forms at depth 1 (opt-in:
     # profiles/r12_rect.txt); such a program is in nobody else's class
     self.rect = bool(fuse_outputs) and kernel_stream2d.rectangular(spec)
@@ -832,22 +848,58 @@ def deep3d_kernels(req, notes):
       yield found
 
 
+LDS_PLANES_NOTE = 'lds_planes'      # key of soda_hip_meta
+
+
+def lds3d_kernels(req, notes):
+  """3-D programs no other family gave a fused depth-1 kernel, when generate() was asked
+  for LDS planes: kernel_stream3d_lds, in the first shape that fits.  Comes last in
+  FAMILIES.  What it did goes into req.lds_note (soda_hip_meta: `lds_planes`), not into
+  `notes`: apart from the metadata, the text of a program this form does not take is the
+  same with and without the switch."""
+  spec = req.spec
+  req.lds_note = None
+  if not req.lds_planes:
+    return
+  if spec['dim'] != 3:
+    req.lds_note = 'not fused: the LDS-plane form handles 3-D programs'
+    return
+  have = [e['name'] for e in req.made if e['kind'] == 'fused' and e['depth'] == 1]
+  if have:
+    req.lds_note = 'not wanted: %s' % have[0]
+    return
+  options = form_options('stream3d_lds', req.options)
+  shape = options.get('lds_shape')
+  found, error = first_fusable(spec, 1, [(kernel_stream3d_lds.emit, dict(
+      zip(('waves', 'rows', 'lanes_x'), shape)) if shape else {})])
+  if found is None:
+    req.lds_note = 'not fused: %s' % error
+    return
+  req.lds_note = found[1]['name']
+  yield found
+
+
 # the kernel families in the order their kernels enter the table; each yields the
 # (text, entry) of the kernels it selects for this request and appends to `notes`
 FAMILIES = (fields2d_kernels, fields3d_kernels, fields1d_kernels, stream1d_kernels,
-            stream2d_kernels, stream3d_kernels, deep3d_kernels)
+            stream2d_kernels, stream3d_kernels, deep3d_kernels, lds3d_kernels)
 
 
 def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
              fused=True, depths=None, inline=True, wave_groups=None,
-             fuse_outputs=False, **fused_options):
+             fuse_outputs=False, lds_planes=False, **fused_options):
   """Returns (kernel text, kernel table).  `depths` overrides the default set
   of fused depths (depth 1 is always included: the scheduler needs it).
   `fuse_outputs`: a one-pass 2-D / 3-D program with several outputs that is not
   multi_field (kernel_stream2d.rectangular) gets ONE fused depth-1 kernel that stores
   every output (kernel_fields2d / kernel_fields3d) besides its per-stage kernels; the
   run-time launches it under a depth limit of 1 (soda_hip_plan_set_max_depth).  Without
-  it such a program keeps per-stage kernels only."""
+  it such a program keeps per-stage kernels only.
+  `lds_planes`: a 3-D program of one stage that no other form gives a fused depth-1 kernel
+  (a window wider than a lane's columns: stars of radius 3 and up) gets the LDS-plane
+  kernel `<app>_fused_k1l` (kernel_stream3d_lds); every other program keeps its table and,
+  apart from the entry `lds_planes` of soda_hip_meta that says what the switch did, its
+  text.  Without it nothing changes."""
   # kernels are generated from the LOWERED program (pointwise-only locals folded
   # into their readers); the blob is still identified by the source program
   source = spec
@@ -863,16 +915,19 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   parts.append(text)
   notes = []
   req = Request(spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
-                fused_options, fuse_outputs=fuse_outputs)
+                fused_options, fuse_outputs=fuse_outputs, lds_planes=lds_planes)
   for family in FAMILIES if fused else ():
     for ftext, entry in family(req, notes):
       parts.append(ftext)
       table.append(annotate_cost(entry, spec))
+      req.made.append(entry)
   if notes:
     parts.append(''.join('// %s\n' % n for n in notes))
-  parts.append(kernel_common.meta_symbol(
-      spec, table, extra=dict(program_hash=kernel_common.program_hash(source),
-                              source_stages=[s['name'] for s in source['stages']])))
+  extra = dict(program_hash=kernel_common.program_hash(source),
+               source_stages=[s['name'] for s in source['stages']])
+  if getattr(req, 'lds_note', None):
+    extra[LDS_PLANES_NOTE] = req.lds_note
+  parts.append(kernel_common.meta_symbol(spec, table, extra=extra))
   return '\n'.join(parts), table
 
 

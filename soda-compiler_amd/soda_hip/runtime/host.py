@@ -484,17 +484,18 @@ class Program:
     return dict(kernel_us=t.kernel_us, launches=t.launches, max_depth=t.max_depth)
 
 
-def open_program(blob=None, source=None, spec=None, fuse_outputs=False):
+def open_program(blob=None, source=None, spec=None, fuse_outputs=False, lds_planes=False):
   """`blob`: path to a code object or to kernel text; `source`: kernel text.  With
   neither, the kernels are generated from `spec` and compiled on the spot (hiprtc);
-  `fuse_outputs` is kernel.generate's switch of that name."""
+  `fuse_outputs` and `lds_planes` are kernel.generate's switches of those names."""
   if blob is not None:
     b = Blob.from_file(blob)
   elif source is not None:
     b = Blob.from_source(source)
   elif spec is not None:
     from ..codegen import kernel
-    b = Blob.from_source(kernel.generate(spec, fuse_outputs=fuse_outputs)[0])
+    b = Blob.from_source(kernel.generate(spec, fuse_outputs=fuse_outputs,
+                                         lds_planes=lds_planes)[0])
   else:
     raise ValueError('need a blob path, kernel source or a program spec')
   return Program(b, spec)
@@ -517,7 +518,8 @@ def reference_init(spec, dims):
   return out
 
 
-def app_test(spec, blob, dims, source=None, iterate=None, fuse_outputs=False):
+def app_test(spec, blob, dims, source=None, iterate=None, fuse_outputs=False,
+             lds_planes=False):
   """The generated `int <app>_test(const char* xclbin, const int dims[4])`
   (reference host.py:984-1167): zero-filled arrays, the reference's input
   pattern, one call of `<app>`, CPU re-computation, comparison on the valid
@@ -526,7 +528,8 @@ def app_test(spec, blob, dims, source=None, iterate=None, fuse_outputs=False):
   from . import selfcheck
   iterate = spec['iterate'] if iterate is None else iterate
   dims = [int(v) for v in list(dims)[:spec['dim']]]
-  prog = open_program(blob=blob, source=source, spec=spec, fuse_outputs=fuse_outputs)
+  prog = open_program(blob=blob, source=source, spec=spec, fuse_outputs=fuse_outputs,
+                      lds_planes=lds_planes)
   if fuse_outputs:      # the fused kernel over several outputs runs under a depth limit
     prog.set_max_depth(1)
   try:
