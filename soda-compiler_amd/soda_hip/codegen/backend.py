@@ -21,6 +21,11 @@ This module has the same two, with `--hip-*` flags where the Xilinx one has
   --hip-lds-planes    3-D programs of one stage whose window is wider than a lane's columns
                       (stars of radius 3 and up) get the LDS-plane kernel <app>_fused_k1l
                       (kernel.generate: lds_planes); goes into every product
+  --hip-lds-fields    3-D programs with two or three outputs that read inputs only and whose
+                      window is wider than a lane's columns (a wave time loop handing its
+                      fields on; with --hip-fuse-outputs a high-order gradient) get the
+                      LDS-plane kernel over several outputs <app>_fused_k1lf
+                      (kernel.generate: lds_fields); goes into every product
 
 `-` writes to stdout.  `stencil` may be this project's `frontend.Stencil` or the
 reference's `soda.core.Stencil` (INTEGRATION.md).
@@ -71,6 +76,12 @@ def add_arguments(parser):
                       'stars); it runs in the default schedule')
 
 
+  parser.add_argument('--hip-lds-fields', action='store_true', dest='hip_lds_fields',
+                      help='one fused depth-1 kernel with the in-plane neighbours in LDS '
+                      'for a 3-D program with two or three outputs that read inputs only '
+                      '(launched under a depth limit of 1: soda_hip_plan_set_max_depth)')
+
+
 def to_spec(stencil):
   if isinstance(stencil, dict):
     return stencil
@@ -112,6 +123,7 @@ def print_code(stencil, args):
   warn_ignored_overrides(args)
   max_depth = getattr(args, 'hip_max_depth', None)
   lds_planes = bool(getattr(args, 'hip_lds_planes', False))
+  lds_fields = bool(getattr(args, 'hip_lds_fields', False))
   files = dict(kernel=getattr(args, 'hip_kernel_file', None),
                host=getattr(args, 'hip_host_file', None),
                header=getattr(args, 'hip_header_file', None),
@@ -135,7 +147,8 @@ def print_code(stencil, args):
     text, table = kernel.generate(
         spec, max_depth=max_depth, cols=getattr(args, 'hip_cols', None),
         chunk_rows=getattr(args, 'hip_chunk_rows', None),
-        fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)), lds_planes=lds_planes)
+        fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)), lds_planes=lds_planes,
+        lds_fields=lds_fields)
   if files['kernel']:
     _logger.info('generate HIP kernel code as %s', files['kernel'])
     f, close = _open(files['kernel'])
@@ -146,7 +159,7 @@ def print_code(stencil, args):
     _logger.info('generate host shim as %s', files['host'])
     f, close = _open(files['host'])
     host_shim.print_code(spec, f, fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)),
-                         lds_planes=lds_planes)
+                         lds_planes=lds_planes, lds_fields=lds_fields)
     if close:
       f.close()
   if files['header']:
@@ -159,7 +172,8 @@ def print_code(stencil, args):
     _logger.info('generate C++ host as %s', files['host_cpp'])
     f, close = _open(files['host_cpp'])
     host_cpp.print_code(spec, table, f, lowered=specmod.inline_pointwise(spec),
-                        fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)))
+                        fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)),
+                        lds_fields=lds_fields)
     if close:
       f.close()
   if files['blob']:

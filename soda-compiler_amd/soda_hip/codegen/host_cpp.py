@@ -478,11 +478,11 @@ def print_multi_gpu_fields(spec, w, app, ins, outs, dim, deepest):
   w('  return 0;\n}\n#endif  // SODA_HIP_MULTI_GPU\n\n')
 
 
-def print_code(spec, kernels, out, lowered=None, fuse_outputs=False):
+def print_code(spec, kernels, out, lowered=None, fuse_outputs=False, lds_fields=False):
   """`spec`: the source program (golden loops, entry points); `lowered`: the
   program the kernels were generated from (descriptor literals); `fuse_outputs`: the
   kernels were generated with kernel.generate's switch of that name (as in
-  host_shim.print_code)."""
+  host_shim.print_code); `lds_fields`: the same for that switch."""
   lowered = spec if lowered is None else lowered
   app = spec['app_name']
   dim = spec['dim']
@@ -573,9 +573,10 @@ def print_code(spec, kernels, out, lowered=None, fuse_outputs=False):
   w('  soda_hip_kernel kernels[%d];\n  const int n_kernels = fill_kernels(kernels);\n'
     % max(1, len(kernels)))
   w('  rc = soda_hip_plan_create(module, &program, kernels, n_kernels, &plan);\n')
-  if fuse_outputs:
-    # generated with --hip-fuse-outputs: the fused kernel over all outputs is not in the
-    # default schedule, a depth limit admits it (soda_hip_plan_set_max_depth)
+  if fuse_outputs or lds_fields:
+    # generated with --hip-fuse-outputs or --hip-lds-fields: the fused kernel over all
+    # outputs is not in the default schedule, a depth limit admits it
+    # (soda_hip_plan_set_max_depth)
     w('  if (rc == 0) rc = soda_hip_plan_set_max_depth(plan, 1);\n')
   w('  if (rc == 0) {\n')
   w('    buffer_t* inputs[] = {%s};\n' % ', '.join('var_%s_buffer' % n for n in ins))

@@ -23,6 +23,9 @@ The unit holds
       3-D, one stage, windows wider than a lane's columns: kernel_stream3d_lds (the
                         in-plane neighbours from an LDS plane), only with `lds_planes=True`
                         and only where no other form made a depth-1 kernel;
+      3-D, two or three outputs that read inputs only, windows wider than a lane's columns:
+                        the same form over several outputs (<app>_fused_k1lf), only with
+                        `lds_fields=True` and only where no other form made a depth-1 kernel;
   * `soda_hip_meta`, JSON describing the program and the kernel table, which
     libsoda_hip.so reads back from the loaded blob.
 
@@ -457,8 +460,10 @@ class Request:
   """What generate() was asked for, normalised once; every family function receives it."""
 
   def __init__(self, spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
-               options, fuse_outputs=False, lds_planes=False):
+               options, fuse_outputs=False, lds_planes=False, lds_fields=False):
     self.spec, self.depths, self.options = spec, depths, options
+    # ... and its form over several outputs (opt-in, the same rule)
+    self.lds_fields = bool(lds_fields)
     # the LDS-plane 3-D form was asked for (opt-in), and the table entries made so far: it
     # is emitted only where they hold no fused depth-1 kernel
     self.lds_planes, self.made = bool(lds_planes), []
@@ -879,15 +884,55 @@ def lds3d_kernels(req, notes):
   yield found
 
 
+LDS_FIELDS_NOTE = 'lds_fields'      # key of soda_hip_meta
+
+
+def lds3d_fields_kernels(req, notes):
+  """Programs with two or more outputs that no other family gave a fused depth-1 kernel, when
+  generate() was asked for LDS planes over fields: kernel_stream3d_lds with fields=True, in
+  the first shape that fits.  Comes last in FAMILIES.  A rectangular program is in this
+  form's class, as in anyone's, only under `fuse_outputs` (Request.rect).  What it did goes
+  into req.lds_fields_note (soda_hip_meta: `lds_fields`) and nowhere else, as for
+  lds3d_kernels."""
+  spec = req.spec
+  req.lds_fields_note = None
+  if not req.lds_fields:
+    return
+  if len(spec['outputs']) < 2:
+    req.lds_fields_note = 'not concerned: one output'
+    return
+  have = [e['name'] for e in req.made if e['kind'] == 'fused' and e['depth'] == 1]
+  if have:
+    req.lds_fields_note = 'not wanted: %s' % have[0]
+    return
+  if spec['dim'] != 3:
+    req.lds_fields_note = 'not fused: the LDS-plane form handles 3-D programs'
+    return
+  if kernel_stream2d.rectangular(spec) and not req.rect:
+    req.lds_fields_note = ('not fused: a one-pass program with several outputs is fused only '
+                           'with fuse_outputs')
+    return
+  options = form_options('stream3d_lds', req.options)
+  shape = options.get('lds_shape')
+  found, error = first_fusable(spec, 1, [(kernel_stream3d_lds.emit, dict(
+      dict(zip(('waves', 'rows', 'lanes_x'), shape)) if shape else {}, fields=True))])
+  if found is None:
+    req.lds_fields_note = 'not fused: %s' % error
+    return
+  req.lds_fields_note = found[1]['name']
+  yield found
+
+
 # the kernel families in the order their kernels enter the table; each yields the
 # (text, entry) of the kernels it selects for this request and appends to `notes`
 FAMILIES = (fields2d_kernels, fields3d_kernels, fields1d_kernels, stream1d_kernels,
-            stream2d_kernels, stream3d_kernels, deep3d_kernels, lds3d_kernels)
+            stream2d_kernels, stream3d_kernels, deep3d_kernels, lds3d_kernels,
+            lds3d_fields_kernels)
 
 
 def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
              fused=True, depths=None, inline=True, wave_groups=None,
-             fuse_outputs=False, lds_planes=False, **fused_options):
+             fuse_outputs=False, lds_planes=False, lds_fields=False, **fused_options):
   """Returns (kernel text, kernel table).  `depths` overrides the default set
   of fused depths (depth 1 is always included: the scheduler needs it).
   `fuse_outputs`: a one-pass 2-D / 3-D program with several outputs that is not
@@ -899,7 +944,14 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   (a window wider than a lane's columns: stars of radius 3 and up) gets the LDS-plane
   kernel `<app>_fused_k1l` (kernel_stream3d_lds); every other program keeps its table and,
   apart from the entry `lds_planes` of soda_hip_meta that says what the switch did, its
-  text.  Without it nothing changes."""
+  text.  Without it nothing changes.
+  `lds_fields`: the same form over several outputs, `<app>_fused_k1lf`, for a 3-D program
+  with two or three outputs that read inputs only (a wave time loop handing its fields on,
+  a high-order gradient - the latter with `fuse_outputs` as well) and that no other form
+  gives a fused depth-1 kernel; launched under a depth limit of 1 like every fused kernel
+  over several outputs.  Every other program keeps its table and, apart from the entry
+  `lds_fields` of soda_hip_meta, its text.  The two LDS switches concern disjoint programs
+  and may be given together."""
   # kernels are generated from the LOWERED program (pointwise-only locals folded
   # into their readers); the blob is still identified by the source program
   source = spec
@@ -915,7 +967,8 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   parts.append(text)
   notes = []
   req = Request(spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
-                fused_options, fuse_outputs=fuse_outputs, lds_planes=lds_planes)
+                fused_options, fuse_outputs=fuse_outputs, lds_planes=lds_planes,
+                lds_fields=lds_fields)
   for family in FAMILIES if fused else ():
     for ftext, entry in family(req, notes):
       parts.append(ftext)
@@ -927,6 +980,8 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
                source_stages=[s['name'] for s in source['stages']])
   if getattr(req, 'lds_note', None):
     extra[LDS_PLANES_NOTE] = req.lds_note
+  if getattr(req, 'lds_fields_note', None):
+    extra[LDS_FIELDS_NOTE] = req.lds_fields_note
   parts.append(kernel_common.meta_symbol(spec, table, extra=extra))
   return '\n'.join(parts), table
 

@@ -25,10 +25,20 @@ Scope: one stage that is the one output, any number of inputs, one element width
 bytes, and per input ONE plane offset at which it is read off the z axis.  Depth 1 only.
 Array edges as in kernel_stream3d: loads clamped into the array on all six sides, stores
 inside the box only, any array size.
+
+`fields=True` is the form over SEVERAL outputs, `<app>_fused_k1lf`: two or three stages that
+are all outputs and read inputs only, in a multi_field program (a wave time loop: the new
+field, the old field and the velocity model handed on) or a rectangular one (a high-order
+gradient).  A Field is then the union of every stage's reads of that input.  Each output has
+a box of its own under kernel_fields3d's contract: the launch's box is the intersection,
+param[1 + j] carries output j's six extras, tiles and z chunks cover the union, and output
+j stores a cell only inside j's box on all three axes.  An output that is one load at
+(0, 0, 0) of an input of its own type is stored straight from the window registers.
 """
 from . import spec as specmod
 from .kernel_common import builtin_type, cell_assignment, tensor_index
-from .kernel_stream2d import LANES, NotFusable
+from .kernel_fields3d import MAX_OUTPUTS
+from .kernel_stream2d import LANES, NotFusable, multi_field, rectangular
 
 LDS_CAP = 65536
 # (wavefronts, rows per lane, lanes per tile row) that emit() chooses from when the caller
@@ -36,8 +46,8 @@ LDS_CAP = 65536
 SHAPES = tuple((w, rw, lx) for w in (8, 4) for rw in (4, 2, 1) for lx in (64, 32, 16))
 
 
-def kernel_name(spec):
-  return '%s_fused_k1l' % spec['app_name']
+def kernel_name(spec, fields=False):
+  return '%s_fused_k1l%s' % (spec['app_name'], 'f' if fields else '')
 
 
 class Field:
@@ -85,6 +95,59 @@ def analyse(spec):
   return stage, fields
 
 
+def analyse_fields(spec):
+  """(stages, [Field]) of a program in the scope of the form over several outputs."""
+  if spec['dim'] != 3:
+    raise NotFusable('the LDS-plane form handles 3-D programs')
+  if not 2 <= len(spec['outputs']) <= MAX_OUTPUTS:
+    raise NotFusable('%d outputs: the LDS-plane form over fields stores 2 to %d'
+                     % (len(spec['outputs']), MAX_OUTPUTS))
+  produced = [s['name'] for s in spec['stages']]
+  for stage in spec['stages']:
+    for name, _ in stage['loads']:
+      if name in produced:
+        raise NotFusable('stage %s reads stage %s: the LDS-plane form over fields takes '
+                         'stages that read inputs only' % (stage['name'], name))
+  if produced != list(spec['outputs']):
+    raise NotFusable('%d stages for %d outputs: the LDS-plane form over fields takes stages '
+                     'that are outputs' % (len(produced), len(spec['outputs'])))
+  if not (multi_field(spec) or rectangular(spec)):
+    raise NotFusable('iterate %d over %d input(s) and %d output(s) that do not feed each '
+                     'other pairwise' % (spec['iterate'], len(spec['inputs']),
+                                         len(spec['outputs'])))
+  types = specmod.tensor_c_types(spec)
+  widths = sorted({specmod.ELEM_SIZE[t] for t in types.values()})
+  if len(widths) > 1:
+    raise NotFusable('mixed element widths')
+  if widths[0] not in (4, 8):
+    raise NotFusable('%d-byte elements: the LDS-plane form handles 4- and 8-byte ones'
+                     % widths[0])
+  fields = []
+  for t in spec['inputs']:
+    rels = []
+    for stage in spec['stages']:
+      rels += [tuple(rel) for name, rel in stage['loads']
+               if name == t['name'] and tuple(rel) not in rels]
+    if rels:
+      fields.append(Field(t['name'], t['c_type'], rels))
+  if not any(f.lds for f in fields):
+    raise NotFusable('no read off the z axis: nothing for an LDS plane to share')
+  return spec['stages'], fields
+
+
+def passed_through(spec, stage):
+  """The input an output hands on unchanged - one load at (0, 0, 0) of an input of the
+  output's own type - or None."""
+  loads = [(name, tuple(rel)) for name, rel in stage['loads']]
+  if stage['lets'] or len(loads) != 1 or loads[0][1] != (0, 0, 0):
+    return None
+  name = loads[0][0]
+  if stage['expr'].strip('() ') != '{%s:0,0,0}' % name:
+    return None
+  types = {t['name']: t['c_type'] for t in spec['inputs']}
+  return name if types.get(name) == stage['c_type'] else None
+
+
 def geometry(fields, elem, waves, rows, lanes_x):
   """Tile, LDS slot and halo of one shape, all in cells."""
   C = 16 // elem
@@ -117,20 +180,21 @@ def lds_vectors(fields, C, rows):
   return seen
 
 
-def estimate_vgprs(fields, elem, geo, rows):
+def estimate_vgprs(fields, elem, geo, rows, computed=1):
+  """`computed`: the outputs whose cells are computed (all but those passed through)."""
   per, C = max(1, elem // 4), geo['C']
   shared = [f for f in fields if f.lds]
   halo_loads = -(-geo['halo_vectors'] // geo['threads'])
   return (sum(f.keep for f in fields) * rows * C * per +     # windows, planes ahead
           len(lds_vectors(fields, C, rows)) * 4 +            # neighbours out of LDS
-          rows * C * per +                                   # the output cells
+          computed * rows * C * per +                        # the output cells
           halo_loads * (4 * len(shared) + 5) + 24)           # halo ring and its addresses
 
 
-def shapes_by_loaded_cells(spec, shapes=SHAPES):
+def shapes_by_loaded_cells(spec, shapes=SHAPES, fields=False):
   """The shapes ordered by cells loaded over cells stored, (TX + hx)(TY + hy) / (TX TY),
   least first (among equals as listed: more wavefronts, taller lanes first)."""
-  _, fields = analyse(spec)
+  _, fields = analyse_fields(spec) if fields else analyse(spec)
   elem = specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
   return sorted(shapes, key=lambda s: geometry(fields, elem, *s)['loaded'])
 
@@ -153,22 +217,30 @@ def rotation(fields, max_period):
 
 
 def emit(spec, depth=1, waves=None, rows=None, lanes_x=None, chunk_planes=64,
-         max_period=16, vgpr_budget=250):
+         max_period=16, vgpr_budget=250, fields=False):
   """Returns (text, kernel table entry).  Without a shape: the first of
-  shapes_by_loaded_cells that fits the register budget and the LDS cap."""
+  shapes_by_loaded_cells that fits the register budget and the LDS cap.  `fields`: the
+  form over several outputs, each stored inside its own box."""
   if depth != 1:
     raise NotFusable('the LDS-plane form is depth 1')
-  stage, fields = analyse(spec)
+  several = bool(fields)
+  if several:
+    stages, fields = analyse_fields(spec)
+  else:
+    stage, fields = analyse(spec)
+    stages = [stage]
   types = specmod.tensor_c_types(spec)
   index = tensor_index(spec)
   out_name = spec['outputs'][0]
   elem = specmod.ELEM_SIZE[types[out_name]]
+  # per output, the input it hands on unchanged (stored from the window, no cells of its own)
+  through = [passed_through(spec, st) if several else None for st in stages]
   if waves is None:
     error = None
-    for shape in shapes_by_loaded_cells(spec):
+    for shape in shapes_by_loaded_cells(spec, fields=several):
       try:
         return emit(spec, depth, *shape, chunk_planes=chunk_planes, max_period=max_period,
-                    vgpr_budget=vgpr_budget)
+                    vgpr_budget=vgpr_budget, fields=several)
       except NotFusable as e:
         error = error or e
     raise error
@@ -180,15 +252,16 @@ def emit(spec, depth=1, waves=None, rows=None, lanes_x=None, chunk_planes=64,
   if geo['lds_bytes'] > LDS_CAP:
     raise NotFusable('%s would need %d bytes of LDS (cap %d)' % (shape_text, geo['lds_bytes'],
                                                                   LDS_CAP))
-  est_vgprs = estimate_vgprs(fields, elem, geo, RW)
+  est_vgprs = estimate_vgprs(fields, elem, geo, RW, computed=through.count(None))
   if est_vgprs > vgpr_budget:
     raise NotFusable('%s would need about %d VGPRs (budget %d)' % (shape_text, est_vgprs,
                                                                     vgpr_budget))
   period, slots = rotation(fields, max_period)
   fill = max(f.zhi - f.zlo + 1 for f in fields)
   shared = [f for f in fields if f.lds]
-  name = kernel_name(spec)
+  name = kernel_name(spec, several)
   T_out = builtin_type(types[out_name])
+  n_out = len(stages)
   # the halo ring of a slot as a list of vectors: the rows above and below at full pitch,
   # then the vectors left and right of the tile's own rows
   PV, TXV, HXLV, SV = PITCH // C, TX // C, HXL // C, (HXL + HXH) // C
@@ -199,8 +272,8 @@ def emit(spec, depth=1, waves=None, rows=None, lanes_x=None, chunk_planes=64,
 
   o = []
   line = o.append
-  line('// fused depth-1 3-D kernel, LDS planes: %s, halo x %d+%d y %d+%d,'
-       % (shape_text, HXL, HXH, HYL, HYH))
+  line('// fused depth-1 3-D kernel%s, LDS planes: %s, halo x %d+%d y %d+%d,'
+       % (' over %d outputs' % n_out if several else '', shape_text, HXL, HXH, HYL, HYH))
   line('// %d bytes of LDS, rotation period %d, %d planes walked before the first stored one, '
        '~%d VGPRs' % (geo['lds_bytes'], period, fill, est_vgprs))
   for f in fields:
@@ -208,16 +281,26 @@ def emit(spec, depth=1, waves=None, rows=None, lanes_x=None, chunk_planes=64,
         f.name, f.zlo, f.zhi, slots[f.name],
         ', plane %+d in LDS' % f.zc if f.lds else ''))
   vec, lvec = {}, {}
-  for c_type in sorted({f.c_type for f in fields} | {types[out_name]}):
+  for c_type in sorted({f.c_type for f in fields} | {st['c_type'] for st in stages}):
     vec[c_type] = 'vec_%s_%s' % (name, c_type)
     lvec[c_type] = 'lvec_%s_%s' % (name, c_type)
     line('typedef %s %s __attribute__((ext_vector_type(%d), aligned(%d)));'
          % (builtin_type(c_type), vec[c_type], C, elem))
     line('typedef %s %s __attribute__((ext_vector_type(%d), aligned(16)));'
          % (builtin_type(c_type), lvec[c_type], C))
+  if several:
+    # which of its cells a lane stores does not change along the plane loop: hoisted out of
+    # it, each such condition would stay a 64-bit lane mask in a pair of SGPRs, for every
+    # row, column and output - more than the scalar file has.  Passed through an empty asm
+    # the lane's bits are opaque and the conditions are computed where they are used
+    # (kernel_fields3d: the same device)
+    line('template <typename T> DEV void %s_opaque(T& v) { asm volatile("" : "+v"(v)); }'
+         % name)
   line('template <bool INTERIOR>')
-  line('DEV void %s_tile(const soda_hip_args& a, const i64 xs, const i64 ys, const i64 z0, '
+  line('DEV void %s_tile(const soda_hip_args& a, %sconst i64 xs, const i64 ys, const i64 z0, '
        'const i64 z1, const int tid%s) {' % (name, ''.join(
+           'const int cells%d, const int sn_lo%d, const int sn_hi%d, ' % (j, j, j)
+           for j in range(n_out if several else 0)), ''.join(
            ', %s (*lds_%s)[%d][%d]' % (builtin_type(f.c_type), f.name, ROWS, PITCH)
            for f in shared)))
   line('  const i64 W = a.dims[0], H = a.dims[1], D = a.dims[2];')
@@ -228,7 +311,11 @@ def emit(spec, depth=1, waves=None, rows=None, lanes_x=None, chunk_planes=64,
     T = builtin_type(f.c_type)
     line('  const %s* __restrict__ g_%s = (const %s*)a.tensor[%d];' % (T, f.name, T,
                                                                       index[f.name]))
-  line('  %s* __restrict__ g_out = (%s*)a.tensor[%d];' % (T_out, T_out, index[out_name]))
+  if not several:
+    line('  %s* __restrict__ g_out = (%s*)a.tensor[%d];' % (T_out, T_out, index[out_name]))
+  for j, st in enumerate(stages if several else ()):
+    T = builtin_type(st['c_type'])
+    line('  %s* __restrict__ g_out%d = (%s*)a.tensor[%d];' % (T, j, T, index[st['name']]))
   # the lane's own rows and columns, clamped into the array (what a clamp changes feeds only
   # cells outside the box)
   line('  i64 row_off[%d], col[%d];' % (RW, C))
@@ -325,32 +412,68 @@ def emit(spec, depth=1, waves=None, rows=None, lanes_x=None, chunk_planes=64,
       line('        const %s l_%s_%s_%s = *(const %s*)&lds_%s[%d][%d + ly + %d][%d + lx * %d + %d];'
            % (lvec[f.c_type], fname, str(ry).replace('-', 'm'), str(vi).replace('-', 'm'),
               lvec[f.c_type], fname, u % 2, HYL, ry, HXL, C, vi * C))
-    line('        %s out_cells[%d][%d];' % (T_out, RW, C))
-    for r in range(RW):
-      for c in range(C):
-        def load(tensor, rel, u=u, r=r, c=c):
-          f = by_name[tensor]
-          dx, dy, dz = rel
-          if (dx, dy) == (0, 0):
-            return own(f, u, dz, r, c)
-          ry, vi, e = r + dy, (c + dx) // C, (c + dx) % C
-          if vi == 0 and 0 <= ry < RW:
-            return own(f, u, dz, ry, e)
-          return 'l_%s_%s_%s[%d]' % (tensor, str(ry).replace('-', 'm'),
-                                     str(vi).replace('-', 'm'), e)
-        cell_assignment(stage, 'out_cells[%d][%d]' % (r, c), load, line, '        ')
-    line('        %s* q = g_out + z * plane;' % T_out)
-    for r in range(RW):
-      line('        if (y + %d >= a.box_lo[1] && y + %d < a.box_hi[1]) {' % (r, r))
-      line('          if (x >= a.box_lo[0] && x + %d <= a.box_hi[0]) {' % C)
-      line('            %s v;%s *(%s*)(q + row_off[%d] + x) = v;' % (
-          vec[types[out_name]], ''.join(' v[%d] = out_cells[%d][%d];' % (c, r, c)
-                                        for c in range(C)), vec[types[out_name]], r))
-      line('          } else {')
-      for c in range(C):
-        line('            if (x + %d >= a.box_lo[0] && x + %d < a.box_hi[0]) '
-             'q[row_off[%d] + x + %d] = out_cells[%d][%d];' % (c, c, r, c, r, c))
-      line('          }')
+    def load_of(u, r, c):
+      def load(tensor, rel):
+        f = by_name[tensor]
+        dx, dy, dz = rel
+        if (dx, dy) == (0, 0):
+          return own(f, u, dz, r, c)
+        ry, vi, e = r + dy, (c + dx) // C, (c + dx) % C
+        if vi == 0 and 0 <= ry < RW:
+          return own(f, u, dz, ry, e)
+        return 'l_%s_%s_%s[%d]' % (tensor, str(ry).replace('-', 'm'),
+                                   str(vi).replace('-', 'm'), e)
+      return load
+
+    if not several:
+      line('        %s out_cells[%d][%d];' % (T_out, RW, C))
+      for r in range(RW):
+        for c in range(C):
+          cell_assignment(stage, 'out_cells[%d][%d]' % (r, c), load_of(u, r, c), line,
+                          '        ')
+      line('        %s* q = g_out + z * plane;' % T_out)
+      for r in range(RW):
+        line('        if (y + %d >= a.box_lo[1] && y + %d < a.box_hi[1]) {' % (r, r))
+        line('          if (x >= a.box_lo[0] && x + %d <= a.box_hi[0]) {' % C)
+        line('            %s v;%s *(%s*)(q + row_off[%d] + x) = v;' % (
+            vec[types[out_name]], ''.join(' v[%d] = out_cells[%d][%d];' % (c, r, c)
+                                          for c in range(C)), vec[types[out_name]], r))
+        line('          } else {')
+        for c in range(C):
+          line('            if (x + %d >= a.box_lo[0] && x + %d < a.box_hi[0]) '
+               'q[row_off[%d] + x + %d] = out_cells[%d][%d];' % (c, c, r, c, r, c))
+        line('          }')
+        line('        }')
+    if several:
+      line('        const int m = (int)n + %d;' % u)
+    for j, st in enumerate(stages if several else ()):
+      # output j: the planes, rows and columns of its own box
+      T, V = builtin_type(st['c_type']), vec[st['c_type']]
+      line('        int mine%d = m >= sn_lo%d && m < sn_hi%d ? cells%d : 0; %s_opaque(mine%d);'
+           % (j, j, j, j, name, j))
+      line('        if (mine%d) {  // %s' % (j, st['name']))
+      if through[j] is None:
+        line('          %s out_cells[%d][%d];' % (T, RW, C))
+        for r in range(RW):
+          for c in range(C):
+            cell_assignment(st, 'out_cells[%d][%d]' % (r, c), load_of(u, r, c), line,
+                            '          ')
+        cell = lambda r, c: 'out_cells[%d][%d]' % (r, c)
+      else:     # handed on: the lane's own cells of plane z, as they lie in the window
+        cell = lambda r, c, f=by_name[through[j]], u=u: own(f, u, 0, r, c)
+      line('          %s* q = g_out%d + z * plane;' % (T, j))
+      for r in range(RW):
+        whole = ((1 << C) - 1) << (r * C)
+        line('          if (mine%d & %d) {' % (j, whole))
+        line('            if ((mine%d & %d) == %d) {' % (j, whole, whole))
+        line('              %s v;%s *(%s*)(q + row_off[%d] + x) = v;' % (
+            V, ''.join(' v[%d] = %s;' % (c, cell(r, c)) for c in range(C)), V, r))
+        line('            } else {')
+        for c in range(C):
+          line('              if (mine%d & %d) q[row_off[%d] + x + %d] = %s;' % (
+              j, 1 << (r * C + c), r, c, cell(r, c)))
+        line('            }')
+        line('          }')
       line('        }')
     line('      }')
     # the other slot gets the next step's plane: own cells from the window, halo ring
@@ -374,17 +497,68 @@ def emit(spec, depth=1, waves=None, rows=None, lanes_x=None, chunk_planes=64,
     line('  __attribute__((shared, aligned(16))) %s lds_%s[2][%d][%d];' % (
         builtin_type(f.c_type), f.name, ROWS, PITCH))
   line('  const int tid = __builtin_amdgcn_workitem_id_x();')
-  line('  const i64 x_origin = a.box_lo[0] - a.box_lo[0] %% %d;' % C)
+  lo, hi = ['a.box_lo[%d]' % d for d in range(3)], ['a.box_hi[%d]' % d for d in range(3)]
+  if several:
+    # the union of the outputs' boxes is what tiles and chunks cover (the launcher sizes
+    # the grid by the same rule: csrc/schedule.cpp, make_launch)
+    lo, hi = ['lo%d' % d for d in range(3)], ['hi%d' % d for d in range(3)]
+    for d in range(3):
+      for side, shift, sign in (('lo', 8 * d, '-'), ('hi', 24 + 8 * d, '+')):
+        line('  i64 %s%d = 0;' % (side, d))
+        for j in range(n_out):
+          line('  { const i64 e = (a.param[%d] >> %d) & 255; if (e > %s%d) %s%d = e; }'
+               % (1 + j, shift, side, d, side, d))
+        line('  %s%d = a.box_%s[%d] %s %s%d;' % (side, d, side, d, sign, side, d))
+  line('  const i64 x_origin = %s - %s %% %d;' % (lo[0], lo[0], C))
   line('  const i64 xs = x_origin + (i64)__builtin_amdgcn_workgroup_id_x() * %d;' % TX)
-  line('  const i64 ys = a.box_lo[1] + (i64)__builtin_amdgcn_workgroup_id_y() * %d;' % TY)
+  line('  const i64 ys = %s + (i64)__builtin_amdgcn_workgroup_id_y() * %d;' % (lo[1], TY))
   line('  const i64 chunk = a.param[0] > 0 ? a.param[0] : %d;' % chunk_planes)
-  line('  const i64 z0 = a.box_lo[2] + (i64)__builtin_amdgcn_workgroup_id_z() * chunk;')
+  line('  const i64 z0 = %s + (i64)__builtin_amdgcn_workgroup_id_z() * chunk;' % lo[2])
   # (the same for every work-item of the workgroup: nobody waits at a barrier for them)
-  line('  if (xs >= a.box_hi[0] || ys >= a.box_hi[1] || z0 >= a.box_hi[2]) return;')
-  line('  const i64 z1 = z0 + chunk < a.box_hi[2] ? z0 + chunk : a.box_hi[2];')
+  line('  if (xs >= %s || ys >= %s || z0 >= %s) return;' % tuple(hi))
+  line('  const i64 z1 = z0 + chunk < %s ? z0 + chunk : %s;' % (hi[2], hi[2]))
+  # the box of output j: the launch's box widened by the extras of param[1 + j], each
+  # bound computed where it is used (eighteen 64-bit bounds kept would fill the scalar file)
+  def box_lo(j, d):
+    return '(a.box_lo[%d] - ((a.param[%d] >> %d) & 255))' % (d, 1 + j, 8 * d)
+
+  def box_hi(j, d):
+    return '(a.box_hi[%d] + ((a.param[%d] >> %d) & 255))' % (d, 1 + j, 24 + 8 * d)
+
+  def within(what, first, size):
+    """`what` as a distance from `first`, clamped into [0, size]"""
+    return '(int)(%s - %s < 0 ? 0 : %s - %s > %s ? %s : %s - %s)' % (
+        what, first, what, first, size, size, what, first)
+
+  if several:
+    line('  const int lx = tid %% %d, ly = tid / %d * %d;' % (LX, LX, RW))
+  for j in range(n_out if several else 0):
+    # what output j stores of this tile and chunk, worked out here, once for both paths, and
+    # kept in three VECTOR registers per output (the one-output form leaves a dozen scalar
+    # registers free, fewer than the bounds of three boxes).  Columns and rows: which of
+    # the lane's own cells lie in j's box, bit r * C + c.  Planes: the steps of the plane
+    # loop that compute them (step m computes plane z0 + m - fill)
+    line('  int cells%d = 0;' % j)
+    line('  {')
+    line('    const int sx_lo = %s, sx_hi = %s;' % (within(box_lo(j, 0), 'xs', TX),
+                                                  within(box_hi(j, 0), 'xs', TX)))
+    line('    const int sy_lo = %s, sy_hi = %s;' % (within(box_lo(j, 1), 'ys', TY),
+                                                  within(box_hi(j, 1), 'ys', TY)))
+    for r in range(RW):
+      line('    if (ly + %d >= sy_lo && ly + %d < sy_hi) {%s }' % (r, r, ''.join(
+          ' if (lx * %d + %d >= sx_lo && lx * %d + %d < sx_hi) cells%d |= %d;'
+          % (C, c, C, c, j, 1 << (r * C + c)) for c in range(C))))
+    line('  }')
+    line('  int sn_lo%d = %s + %d, sn_hi%d = %s + %d;' % (
+        j, within(box_lo(j, 2), 'z0', '(z1 - z0)'), fill,
+        j, within(box_hi(j, 2), 'z0', '(z1 - z0)'), fill))
+    line('  %s_opaque(cells%d); %s_opaque(sn_lo%d); %s_opaque(sn_hi%d);'
+         % (name, j, name, j, name, j))
   line('  const bool interior = xs - %d >= 0 && xs + %d <= a.dims[0] && '
        'ys - %d >= 0 && ys + %d <= a.dims[1];' % (HXL, TX + HXH, HYL, TY + HYH))
-  args = 'a, xs, ys, z0, z1, tid%s' % ''.join(', lds_%s' % f.name for f in shared)
+  args = 'a, %sxs, ys, z0, z1, tid%s' % (
+      ''.join('cells%d, sn_lo%d, sn_hi%d, ' % (j, j, j) for j in range(n_out if several else 0)),
+      ''.join(', lds_%s' % f.name for f in shared))
   line('  if (interior) %s_tile<true>(%s);' % (name, args))
   line('  else %s_tile<false>(%s);' % (name, args))
   line('}')
@@ -394,4 +568,6 @@ def emit(spec, depth=1, waves=None, rows=None, lanes_x=None, chunk_planes=64,
                rows=RW, w_out=TX, r_out=TY, period=period, est_vgprs=est_vgprs,
                lds_bytes=geo['lds_bytes'], lds_planes=len(shared), waves=waves,
                halo=[HXL, HXH, HYL, HYH], loaded_cells=loaded)
+  if several:
+    entry['fields'] = n_out
   return '\n'.join(o) + '\n', entry

@@ -484,10 +484,12 @@ class Program:
     return dict(kernel_us=t.kernel_us, launches=t.launches, max_depth=t.max_depth)
 
 
-def open_program(blob=None, source=None, spec=None, fuse_outputs=False, lds_planes=False):
+def open_program(blob=None, source=None, spec=None, fuse_outputs=False, lds_planes=False,
+                 lds_fields=False):
   """`blob`: path to a code object or to kernel text; `source`: kernel text.  With
   neither, the kernels are generated from `spec` and compiled on the spot (hiprtc);
-  `fuse_outputs` and `lds_planes` are kernel.generate's switches of those names."""
+  `fuse_outputs`, `lds_planes` and `lds_fields` are kernel.generate's switches of those
+  names."""
   if blob is not None:
     b = Blob.from_file(blob)
   elif source is not None:
@@ -495,7 +497,7 @@ def open_program(blob=None, source=None, spec=None, fuse_outputs=False, lds_plan
   elif spec is not None:
     from ..codegen import kernel
     b = Blob.from_source(kernel.generate(spec, fuse_outputs=fuse_outputs,
-                                         lds_planes=lds_planes)[0])
+                                         lds_planes=lds_planes, lds_fields=lds_fields)[0])
   else:
     raise ValueError('need a blob path, kernel source or a program spec')
   return Program(b, spec)
@@ -519,7 +521,7 @@ def reference_init(spec, dims):
 
 
 def app_test(spec, blob, dims, source=None, iterate=None, fuse_outputs=False,
-             lds_planes=False):
+             lds_planes=False, lds_fields=False):
   """The generated `int <app>_test(const char* xclbin, const int dims[4])`
   (reference host.py:984-1167): zero-filled arrays, the reference's input
   pattern, one call of `<app>`, CPU re-computation, comparison on the valid
@@ -529,8 +531,8 @@ def app_test(spec, blob, dims, source=None, iterate=None, fuse_outputs=False,
   iterate = spec['iterate'] if iterate is None else iterate
   dims = [int(v) for v in list(dims)[:spec['dim']]]
   prog = open_program(blob=blob, source=source, spec=spec, fuse_outputs=fuse_outputs,
-                      lds_planes=lds_planes)
-  if fuse_outputs:      # the fused kernel over several outputs runs under a depth limit
+                      lds_planes=lds_planes, lds_fields=lds_fields)
+  if fuse_outputs or lds_fields:    # a fused kernel over several outputs: under a depth limit
     prog.set_max_depth(1)
   try:
     inputs = reference_init(spec, dims)

@@ -23,11 +23,18 @@ shipped shape is the first): `--shape-rounds` timed rounds each, median per swee
 code objects come from `--build-candidates` (no GPU needed: hipcc, into the blobs
 directory) or, where that was not run, from a run-time compile.
 
+`--fields`: the same protocol for the form over several outputs (kernel.generate's
+`lds_fields`; acoustic3d, skewwave3d, deriv3d from <app>.ldsf.hsaco, each at its own
+`iterate`).  There `lds` is the blob under set_max_depth(1) - a fused kernel over several
+outputs is not in the default schedule - and per-stage one launch per stage and iteration;
+every output is compared on its own box; no shape candidates are timed.
+
 Registers, LDS and scratch come from the code object's metadata.  `--static` prints the
 derived and the compiler's figures and times nothing (no GPU needed).
 
     python tools/lds3d/lds3d_bench.py [--apps APP ...] [--size W H D] [--sweeps K] [--repeats R]
                                 [--candidates N] [--static] [--build-candidates] [--out FILE]
+                                [--fields]
 """
 import argparse
 import json
@@ -99,17 +106,22 @@ def main():
                   help='the static figures only (registers, LDS, derived traffic): no GPU')
   ap.add_argument('--build-candidates', action='store_true',
                   help='compile the candidates\' code objects (hipcc) and exit: no GPU')
+  ap.add_argument('--fields', action='store_true',
+                  help='the form over several outputs (lds_fields) instead of lds_planes')
   ap.add_argument('--out', default=None)
   args = ap.parse_args()
   assert args.sweeps >= 3
   import __graft_entry__ as entry
   from soda_hip import frontend
   from soda_hip.codegen import kernel, spec as specmod
-  apps = args.apps or list(entry.LDS3D_APPS)
+  apps = args.apps or list(entry.LDS_FIELDS_APPS if args.fields else entry.LDS3D_APPS)
+  if args.fields:
+    args.candidates = 0
   dims = tuple(args.size)
   shape = tuple(reversed(dims))
   lines = [
-      'LDS-plane kernels for high-order 3-D stencils (kernel.generate: lds_planes) against the',
+      'LDS-plane kernels for high-order 3-D stencils (kernel.generate: %s) against the'
+      % ('lds_fields' if args.fields else 'lds_planes'),
       'per-stage schedule.  tools/lds3d/lds3d_bench.py: rounds of %d back-to-back sweeps between device'
       % args.repeats,
       'events, the two schedules alternating, %d untimed rounds, then the median (min .. max) of'
@@ -118,17 +130,27 @@ def main():
       % args.sweeps,
       'more than the spread (the larger max - min).  Bytes per cell are derived from the table,',
       'rates are algorithmic bytes x valid cell-updates over the measured time.  Register and LDS',
-      'figures: code-object metadata (hipcc, gfx950).  Shape candidates: (wavefronts, rows per',
-      'lane, lanes per tile row), %d timed rounds each, median.' % args.shape_rounds, '']
+      'figures: code-object metadata (hipcc, gfx950).'] + ([] if args.fields else [
+          'Shape candidates: (wavefronts, rows per lane, lanes per tile row), %d timed rounds each, '
+          'median.' % args.shape_rounds]) + ['']
   for app in apps:
     spec = specmod.spec_from_stencil(frontend.load(entry.sample_path(app)))
     iterate = spec['iterate']
-    blob = entry.blob_path(app, lds_planes=True)
-    table = kernel.generate(spec, lds_planes=True)[1]
+    if args.fields:
+      from soda_hip.codegen import kernel_stream2d
+      blob = entry.blob_path(app, lds_fields=True)
+      table = kernel.generate(spec, lds_fields=True,
+                              fuse_outputs=kernel_stream2d.rectangular(spec))[1]
+    else:
+      blob = entry.blob_path(app, lds_planes=True)
+      table = kernel.generate(spec, lds_planes=True)[1]
     k = table[-1]
-    assert k['kind'] == 'fused' and k['name'] == app + '_fused_k1l', k
-    shapes = fitting_shapes(spec)[:max(1, args.candidates)]
-    assert shapes[0][1]['tile'] == k['tile'] and shapes[0][1]['block'] == k['block']
+    assert k['kind'] == 'fused' and \
+        k['name'] == app + ('_fused_k1lf' if args.fields else '_fused_k1l'), k
+    stage_names = [e['name'] for e in table if e['kind'] == 'stage']
+    shapes = [] if args.fields else fitting_shapes(spec)[:max(1, args.candidates)]
+    assert args.fields or (shapes[0][1]['tile'] == k['tile'] and
+                           shapes[0][1]['block'] == k['block'])
     if args.build_candidates:
       for cand, _ in shapes[1:]:
         text = kernel.generate(spec, lds_planes=True, lds_shape=cand)[0]
@@ -138,14 +160,14 @@ def main():
     elem = specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
     alg = specmod.algorithmic_bytes_per_update(spec)
     cells = k['tile'][0] * k['tile'][1]
-    n_loads = len(specmod.inline_pointwise(spec)['stages'][0]['loads'])
+    n_loads = sum(len(st['loads']) for st in specmod.inline_pointwise(spec)['stages'])
     static = [
         '  bytes per cell: algorithmic %d; LDS-plane kernel %.2f with its halo (tile %d x %d, '
         '%d wavefronts, %d rows per lane, halo x %d+%d y %d+%d); per-stage %d global loads of '
         '%d B per cell' % ((alg, k['step_bytes'] / float(cells), k['tile'][0], k['tile'][1],
                             k['waves'], k['rows']) + tuple(k['halo']) + (n_loads, elem)),
-        static_line(k['name'], static_figures(blob, k['name'])),
-        static_line(table[0]['name'], static_figures(blob, table[0]['name']))]
+        static_line(k['name'], static_figures(blob, k['name']))] + [
+            static_line(name, static_figures(blob, name)) for name in stage_names]
     if args.static:
       lines.append('%s: NOT MEASURED (static figures only)' % app)
       lines += static
@@ -166,7 +188,7 @@ def main():
       d.upload(a.astype(dt))
       del a
     pin, pout = [d.ptr for d in din], [d.ptr for d in dout]
-    schedules = [('lds', 0), ('per-stage', -1)]
+    schedules = [('lds', 1 if args.fields else 0), ('per-stage', -1)]
     times = {name: [] for name, _ in schedules}
     launches = {}
 
@@ -184,20 +206,24 @@ def main():
         if r >= args.warmup:
           times[name].append(t['kernel_us'] / 1e3)
     assert launches['lds'] == [k['name']] * iterate, launches
-    assert launches['per-stage'] == [table[0]['name']] * iterate, launches
-    # both schedules' results at this size, bit for bit on the output's box
+    assert launches['per-stage'] == stage_names * iterate, launches
+    # both schedules' results at this size, bit for bit on every output's box
     results = {}
     for name, limit in schedules:
       for d in dout:
         d.zero()
       run(prog, name, limit, 1)
       results[name] = [d.download(shape, dt) for d, dt in zip(dout, prog.out_dtypes)]
-    lo, hi = specmod.iteration_boxes(spec, iterate)[-1][spec['outputs'][0]]
-    sl = tuple(slice(-lo[d], dims[d] - hi[d]) for d in (2, 1, 0))
-    a, b = results['lds'][0][sl], results['per-stage'][0][sl]
-    same = bool(np.array_equal(np.ascontiguousarray(a).view(np.uint8),
-                               np.ascontiguousarray(b).view(np.uint8)))
-    reference = np.ascontiguousarray(b).copy()
+    same = True
+    for j, name in enumerate(spec['outputs']):
+      lo, hi = specmod.iteration_boxes(spec, iterate)[-1][name]
+      sl = tuple(slice(-lo[d], dims[d] - hi[d]) for d in (2, 1, 0))
+      a, b = results['lds'][j][sl], results['per-stage'][j][sl]
+      same = same and bool(np.array_equal(np.ascontiguousarray(a).view(np.uint8),
+                                          np.ascontiguousarray(b).view(np.uint8)))
+      if j == 0:      # (the shape candidates below: one output, this slice)
+        reference, sl0 = np.ascontiguousarray(b).copy(), sl
+    sl = sl0
     del results, a, b
     updates = specmod.valid_cells(spec, dims, iterate)
     med = {n: statistics.median(ts) for n, ts in times.items()}
