@@ -15,17 +15,8 @@ This module has the same two, with `--hip-*` flags where the Xilinx one has
                       text (cf. --xocl-hw-xo, which runs the Vivado tools)
   --hip [DIR]         all of the above under default names (cf. --xocl)
 
-  --hip-fuse-outputs  one-pass 2-D / 3-D programs with several outputs that do not feed
-                      the inputs pairwise get one fused depth-1 kernel storing every
-                      output (kernel.generate: fuse_outputs); goes into every product
-  --hip-lds-planes    3-D programs of one stage whose window is wider than a lane's columns
-                      (stars of radius 3 and up) get the LDS-plane kernel <app>_fused_k1l
-                      (kernel.generate: lds_planes); goes into every product
-  --hip-lds-fields    3-D programs with two or three outputs that read inputs only and whose
-                      window is wider than a lane's columns (a wave time loop handing its
-                      fields on; with --hip-fuse-outputs a high-order gradient) get the
-                      LDS-plane kernel over several outputs <app>_fused_k1lf
-                      (kernel.generate: lds_fields); goes into every product
+  one flag per opt-in kernel form, the rows of switches.py (--hip-fuse-outputs,
+  --hip-lds-planes, --hip-lds-fields: INTEGRATION.md); each goes into every product
 
 `-` writes to stdout.  `stencil` may be this project's `frontend.Stencil` or the
 reference's `soda.core.Stencil` (INTEGRATION.md).
@@ -34,7 +25,7 @@ import logging
 import os
 import sys
 
-from . import header, host_cpp, host_shim, kernel
+from . import header, host_cpp, host_shim, kernel, switches
 from . import spec as specmod
 
 _logger = logging.getLogger().getChild(__name__)
@@ -66,20 +57,9 @@ def add_arguments(parser):
                       'by burst width)')
   parser.add_argument('--hip-chunk-rows', type=int, dest='hip_chunk_rows',
                       metavar='ROWS', help='outer-dimension rows per workgroup')
-  parser.add_argument('--hip-fuse-outputs', action='store_true', dest='hip_fuse_outputs',
-                      help='one fused depth-1 kernel for a one-pass 2-D / 3-D program '
-                      'with several outputs (launched under a depth limit of 1: '
-                      'soda_hip_plan_set_max_depth)')
-  parser.add_argument('--hip-lds-planes', action='store_true', dest='hip_lds_planes',
-                      help='one fused depth-1 kernel with the in-plane neighbours in LDS '
-                      'for a one-stage 3-D program no other fused form takes (high-order '
-                      'stars); it runs in the default schedule')
-
-
-  parser.add_argument('--hip-lds-fields', action='store_true', dest='hip_lds_fields',
-                      help='one fused depth-1 kernel with the in-plane neighbours in LDS '
-                      'for a 3-D program with two or three outputs that read inputs only '
-                      '(launched under a depth limit of 1: soda_hip_plan_set_max_depth)')
+  for switch in switches.SWITCHES:
+    parser.add_argument(switch.flag, action='store_true', dest=switch.dest,
+                        help=switch.help)
 
 
 def to_spec(stencil):
@@ -122,8 +102,7 @@ def print_code(stencil, args):
   spec = to_spec(stencil)
   warn_ignored_overrides(args)
   max_depth = getattr(args, 'hip_max_depth', None)
-  lds_planes = bool(getattr(args, 'hip_lds_planes', False))
-  lds_fields = bool(getattr(args, 'hip_lds_fields', False))
+  on = switches.from_args(args)
   files = dict(kernel=getattr(args, 'hip_kernel_file', None),
                host=getattr(args, 'hip_host_file', None),
                header=getattr(args, 'hip_header_file', None),
@@ -146,9 +125,7 @@ def print_code(stencil, args):
   if files['kernel'] or files['blob'] or files['host_cpp']:
     text, table = kernel.generate(
         spec, max_depth=max_depth, cols=getattr(args, 'hip_cols', None),
-        chunk_rows=getattr(args, 'hip_chunk_rows', None),
-        fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)), lds_planes=lds_planes,
-        lds_fields=lds_fields)
+        chunk_rows=getattr(args, 'hip_chunk_rows', None), **on)
   if files['kernel']:
     _logger.info('generate HIP kernel code as %s', files['kernel'])
     f, close = _open(files['kernel'])
@@ -158,8 +135,7 @@ def print_code(stencil, args):
   if files['host']:
     _logger.info('generate host shim as %s', files['host'])
     f, close = _open(files['host'])
-    host_shim.print_code(spec, f, fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)),
-                         lds_planes=lds_planes, lds_fields=lds_fields)
+    host_shim.print_code(spec, f, **on)
     if close:
       f.close()
   if files['header']:
@@ -171,9 +147,7 @@ def print_code(stencil, args):
   if files['host_cpp']:
     _logger.info('generate C++ host as %s', files['host_cpp'])
     f, close = _open(files['host_cpp'])
-    host_cpp.print_code(spec, table, f, lowered=specmod.inline_pointwise(spec),
-                        fuse_outputs=bool(getattr(args, 'hip_fuse_outputs', False)),
-                        lds_fields=lds_fields)
+    host_cpp.print_code(spec, table, f, lowered=specmod.inline_pointwise(spec), **on)
     if close:
       f.close()
   if files['blob']:

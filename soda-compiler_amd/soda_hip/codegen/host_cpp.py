@@ -14,6 +14,7 @@ loop nest and compares (host.py:984-1167).  What the reference bakes in as
 OpenCL boiler-plate is here a handful of descriptor literals for the C ABI.
 """
 from . import spec as specmod
+from . import switches
 from .kernel_common import program_hash, tensor_index
 
 _COORD = 'pqrs'
@@ -478,11 +479,10 @@ def print_multi_gpu_fields(spec, w, app, ins, outs, dim, deepest):
   w('  return 0;\n}\n#endif  // SODA_HIP_MULTI_GPU\n\n')
 
 
-def print_code(spec, kernels, out, lowered=None, fuse_outputs=False, lds_fields=False):
+def print_code(spec, kernels, out, lowered=None, **on):
   """`spec`: the source program (golden loops, entry points); `lowered`: the
-  program the kernels were generated from (descriptor literals); `fuse_outputs`: the
-  kernels were generated with kernel.generate's switch of that name (as in
-  host_shim.print_code); `lds_fields`: the same for that switch."""
+  program the kernels were generated from (descriptor literals); `on`: the switches of
+  kernel.generate the kernels were generated with (as in host_shim.print_code)."""
   lowered = spec if lowered is None else lowered
   app = spec['app_name']
   dim = spec['dim']
@@ -573,9 +573,9 @@ def print_code(spec, kernels, out, lowered=None, fuse_outputs=False, lds_fields=
   w('  soda_hip_kernel kernels[%d];\n  const int n_kernels = fill_kernels(kernels);\n'
     % max(1, len(kernels)))
   w('  rc = soda_hip_plan_create(module, &program, kernels, n_kernels, &plan);\n')
-  if fuse_outputs or lds_fields:
-    # generated with --hip-fuse-outputs or --hip-lds-fields: the fused kernel over all
-    # outputs is not in the default schedule, a depth limit admits it
+  if switches.depth_limit(on):
+    # generated with a switch that makes a fused kernel over all outputs: it is not in the
+    # default schedule, a depth limit admits it
     # (soda_hip_plan_set_max_depth)
     w('  if (rc == 0) rc = soda_hip_plan_set_max_depth(plan, 1);\n')
   w('  if (rc == 0) {\n')

@@ -30,8 +30,11 @@ The unit holds
     libsoda_hip.so reads back from the loaded blob.
 
 generate() is the driver: one function per family (FAMILIES) selects forms, depths and
-options, form_options() says which options a form receives.
+options, form_options() says which options a form receives.  The opt-in forms' switches
+are the rows of switches.py.
 """
+import collections
+import functools
 import hashlib
 import inspect
 import json
@@ -45,6 +48,7 @@ from . import (kernel_common, kernel_fields1d, kernel_fields2d, kernel_fields3d,
                kernel_stream1d, kernel_stream2d, kernel_stream2d_wp, kernel_stream3d,
                kernel_stream3d_blk, kernel_stream3d_lds, kernel_stream3d_wp)
 from . import spec as specmod
+from . import switches
 
 DEFAULT_MAX_DEPTH = 12
 # Wavefronts per strip for deep fused 2-D kernels: 0 = single-wave form only,
@@ -460,16 +464,17 @@ class Request:
   """What generate() was asked for, normalised once; every family function receives it."""
 
   def __init__(self, spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
-               options, fuse_outputs=False, lds_planes=False, lds_fields=False):
+               options, on):
     self.spec, self.depths, self.options = spec, depths, options
-    # ... and its form over several outputs (opt-in, the same rule)
-    self.lds_fields = bool(lds_fields)
-    # the LDS-plane 3-D form was asked for (opt-in), and the table entries made so far: it
-    # is emitted only where they hold no fused depth-1 kernel
-    self.lds_planes, self.made = bool(lds_planes), []
+    # the opt-in forms asked for ({keyword: bool}, codegen/switches.py), what each LDS-plane
+    # form did ({key of soda_hip_meta: note}, lds3d_kernels), and the table entries made so
+    # far: an LDS-plane form is emitted only where they hold no fused depth-1 kernel
+    self.on = {s.keyword: bool(on[s.keyword]) for s in switches.SWITCHES}
+    self.meta_notes, self.made = {}, []
     # one-pass programs with several outputs get the fields forms at depth 1 (opt-in:
     # profiles/r12_rect.txt); such a program is in nobody else's class
-    self.rect = bool(fuse_outputs) and kernel_stream2d.rectangular(spec)
+    fuse_outputs = self.on['fuse_outputs']
+    self.rect = fuse_outputs and kernel_stream2d.rectangular(spec)
     if fuse_outputs and not self.rect and len(spec['outputs']) >= 2 and \
         spec['dim'] in (2, 3) and not kernel_stream2d.multi_field(spec):
       self.rect_refusal = ('outputs not fused: iterate %d over %d input(s) and %d output(s) '
@@ -500,6 +505,33 @@ class Request:
     self.chain = len(self.default_depths) > 1
 
 
+def chain_depths(req):
+  """The depths a multi-field family wants: its defaults, or depth 1 and those asked for."""
+  if req.depths is not None:
+    return sorted(set([1] + list(req.depths)))
+  return req.default_depths
+
+
+def fused_at_depths(req, notes, wanted, attempts_of):
+  """The depth loop of the families that cannot do without their depth-1 kernel: per depth of
+  `wanted` the first of `attempts_of(depth)`, a list of (emit, kwargs), that fuses.  A
+  refused depth leaves a note and the loop goes on - unless it was depth 1: the scheduler
+  needs depth 1, without it the program keeps its per-stage kernels.  attempts_of may raise
+  NotFusable itself: nothing is left to try at this depth or a deeper one."""
+  for depth in wanted:
+    last = depth == 1
+    try:
+      found, error = first_fusable(req.spec, depth, attempts_of(depth))
+    except kernel_stream2d.NotFusable as nothing_to_try:
+      found, error, last = None, nothing_to_try, True
+    if found is not None:
+      yield found
+      continue
+    notes.append('depth %d not fused: %s' % (depth, error))
+    if last:
+      return
+
+
 def fields2d_kernels(req, notes):
   """Multi-field 2-D programs: kernel_fields2d at each depth; rectangular ones, when
   generate() was asked to fuse their outputs, at depth 1."""
@@ -508,18 +540,8 @@ def fields2d_kernels(req, notes):
     notes.append(req.rect_refusal)
   if spec['dim'] != 2 or not (kernel_stream2d.multi_field(spec) or req.rect):
     return
-  wanted = req.default_depths
-  if req.depths is not None:
-    wanted = sorted(set([1] + list(req.depths)))
-  for depth in [1] if req.rect else wanted:
-    found, error = first_fusable(spec, depth, [
-        (kernel_fields2d.emit, dict(req.strip, **form_options('fields2d', req.options)))])
-    if found is None:
-      notes.append('depth %d not fused: %s' % (depth, error))
-      if depth == 1:      # the scheduler needs depth 1: without it, per-stage kernels
-        return
-      continue
-    yield found
+  yield from fused_at_depths(req, notes, [1] if req.rect else chain_depths(req), lambda depth: [
+      (kernel_fields2d.emit, dict(req.strip, **form_options('fields2d', req.options)))])
 
 
 def fields3d_kernels(req, notes):
@@ -531,10 +553,8 @@ def fields3d_kernels(req, notes):
     notes.append(req.rect_refusal)
   if spec['dim'] != 3 or not (kernel_stream2d.multi_field(spec) or req.rect):
     return
-  wanted = req.default_depths
-  if req.depths is not None:
-    wanted = sorted(set([1] + list(req.depths)))
-  for depth in [1] if req.rect else wanted:
+
+  def attempts(depth):
     options = form_options('fields3d', req.options)
     shapes = [s for s in kernel_fields3d.shapes_by_kept_fraction(spec, depth)
               if not req.cols or s[1] == req.cols]
@@ -543,18 +563,11 @@ def fields3d_kernels(req, notes):
     if 'rows' in options:
       shapes = [(options.pop('rows'), req.cols or 2)]
     if not shapes:
-      notes.append('depth %d not fused: %d inputs, 3-D tiles take %d rows x inputs' % (
-          depth, len(spec['inputs']), RECT3D_INPUT_ROWS))
-      return
-    found, error = first_fusable(spec, depth, [
-        (kernel_fields3d.emit, dict(options, rows=rows, cols=lane_cols))
-        for rows, lane_cols in shapes])
-    if found is None:
-      notes.append('depth %d not fused: %s' % (depth, error))
-      if depth == 1:      # the scheduler needs depth 1: without it, per-stage kernels
-        return
-      continue
-    yield found
+      raise kernel_stream2d.NotFusable('%d inputs, 3-D tiles take %d rows x inputs' % (
+          len(spec['inputs']), RECT3D_INPUT_ROWS))
+    return [(kernel_fields3d.emit, dict(options, rows=rows, cols=lane_cols))
+            for rows, lane_cols in shapes]
+  yield from fused_at_depths(req, notes, [1] if req.rect else chain_depths(req), attempts)
 
 
 def fields1d_kernels(req, notes):
@@ -562,19 +575,9 @@ def fields1d_kernels(req, notes):
   spec = req.spec
   if spec['dim'] != 1 or not kernel_stream2d.multi_field(spec):
     return
-  wanted = req.default_depths
-  if req.depths is not None:
-    wanted = sorted(set([1] + list(req.depths)))
-  for depth in wanted:
-    found, error = first_fusable(spec, depth, [
-        (kernel_fields1d.emit, dict(form_options('fields1d', req.options),
-                                    cols=req.strip['cols']))])
-    if found is None:
-      notes.append('depth %d not fused: %s' % (depth, error))
-      if depth == 1:      # the scheduler needs depth 1: without it, per-stage kernels
-        return
-      continue
-    yield found
+  yield from fused_at_depths(req, notes, chain_depths(req), lambda depth: [
+      (kernel_fields1d.emit, dict(form_options('fields1d', req.options),
+                                  cols=req.strip['cols']))])
 
 
 def stream1d_kernels(req, notes):
@@ -585,16 +588,9 @@ def stream1d_kernels(req, notes):
   wanted = [d for d in req.default_depths if d in STREAM1D_DEPTHS]
   if req.depths is not None:
     wanted = sorted(set([1] + [d for d in req.depths if req.chain or d == 1]))
-  for depth in wanted:
-    found, error = first_fusable(spec, depth, [
-        (kernel_stream1d.emit, dict(form_options('stream1d', req.options),
-                                    cols=req.strip['cols']))])
-    if found is None:
-      notes.append('depth %d not fused: %s' % (depth, error))
-      if depth == 1:      # the scheduler needs depth 1: without it, per-stage kernels
-        return
-      continue
-    yield found
+  yield from fused_at_depths(req, notes, wanted, lambda depth: [
+      (kernel_stream1d.emit, dict(form_options('stream1d', req.options),
+                                  cols=req.strip['cols']))])
 
 
 def stream2d_depths(req):
@@ -853,81 +849,53 @@ def deep3d_kernels(req, notes):
       yield found
 
 
-LDS_PLANES_NOTE = 'lds_planes'      # key of soda_hip_meta
+# The two LDS-plane forms (kernel_stream3d_lds), one per switch.  `fields`: the form over
+# several outputs.  `refusals`: in the order they are checked, (condition, note) over the
+# request and the name of a fused depth-1 kernel another family made ('' if none).  A
+# rectangular program is in the fields form's class, as in anyone's, only under
+# `fuse_outputs` (Request.rect).
+LdsForm = collections.namedtuple('LdsForm', 'switch fields refusals')
+_NOT_3D = (lambda req, have: req.spec['dim'] != 3,
+           'not fused: the LDS-plane form handles 3-D programs')
+_NOT_WANTED = (lambda req, have: bool(have), 'not wanted: {have}')
+LDS_PLANES = LdsForm('lds_planes', False, (_NOT_3D, _NOT_WANTED))
+LDS_FIELDS = LdsForm('lds_fields', True, (
+    (lambda req, have: len(req.spec['outputs']) < 2, 'not concerned: one output'),
+    _NOT_WANTED, _NOT_3D,
+    (lambda req, have: kernel_stream2d.rectangular(req.spec) and not req.rect,
+     'not fused: a one-pass program with several outputs is fused only with fuse_outputs')))
 
 
-def lds3d_kernels(req, notes):
+def lds3d_kernels(form, req, notes):
   """3-D programs no other family gave a fused depth-1 kernel, when generate() was asked
-  for LDS planes: kernel_stream3d_lds, in the first shape that fits.  Comes last in
-  FAMILIES.  What it did goes into req.lds_note (soda_hip_meta: `lds_planes`), not into
-  `notes`: apart from the metadata, the text of a program this form does not take is the
-  same with and without the switch."""
-  spec = req.spec
-  req.lds_note = None
-  if not req.lds_planes:
+  for this LDS-plane form: kernel_stream3d_lds, in the first shape that fits.  The two forms
+  come last in FAMILIES.  What a form did goes into req.meta_notes under its switch's key of
+  soda_hip_meta, not into `notes`: apart from the metadata, the text of a program the form
+  does not take is the same with and without the switch."""
+  if not req.on[form.switch]:
     return
-  if spec['dim'] != 3:
-    req.lds_note = 'not fused: the LDS-plane form handles 3-D programs'
-    return
-  have = [e['name'] for e in req.made if e['kind'] == 'fused' and e['depth'] == 1]
-  if have:
-    req.lds_note = 'not wanted: %s' % have[0]
-    return
-  options = form_options('stream3d_lds', req.options)
-  shape = options.get('lds_shape')
-  found, error = first_fusable(spec, 1, [(kernel_stream3d_lds.emit, dict(
-      zip(('waves', 'rows', 'lanes_x'), shape)) if shape else {})])
+  key = switches.BY_KEYWORD[form.switch].note
+  have = ([e['name'] for e in req.made if e['kind'] == 'fused' and e['depth'] == 1] + [''])[0]
+  for refused, note in form.refusals:
+    if refused(req, have):
+      req.meta_notes[key] = note.format(have=have)
+      return
+  shape = form_options('stream3d_lds', req.options).get('lds_shape')
+  found, error = first_fusable(req.spec, 1, [(kernel_stream3d_lds.emit, dict(
+      dict(zip(('waves', 'rows', 'lanes_x'), shape)) if shape else {}, fields=form.fields))])
   if found is None:
-    req.lds_note = 'not fused: %s' % error
+    req.meta_notes[key] = 'not fused: %s' % error
     return
-  req.lds_note = found[1]['name']
-  yield found
-
-
-LDS_FIELDS_NOTE = 'lds_fields'      # key of soda_hip_meta
-
-
-def lds3d_fields_kernels(req, notes):
-  """Programs with two or more outputs that no other family gave a fused depth-1 kernel, when
-  generate() was asked for LDS planes over fields: kernel_stream3d_lds with fields=True, in
-  the first shape that fits.  Comes last in FAMILIES.  A rectangular program is in this
-  form's class, as in anyone's, only under `fuse_outputs` (Request.rect).  What it did goes
-  into req.lds_fields_note (soda_hip_meta: `lds_fields`) and nowhere else, as for
-  lds3d_kernels."""
-  spec = req.spec
-  req.lds_fields_note = None
-  if not req.lds_fields:
-    return
-  if len(spec['outputs']) < 2:
-    req.lds_fields_note = 'not concerned: one output'
-    return
-  have = [e['name'] for e in req.made if e['kind'] == 'fused' and e['depth'] == 1]
-  if have:
-    req.lds_fields_note = 'not wanted: %s' % have[0]
-    return
-  if spec['dim'] != 3:
-    req.lds_fields_note = 'not fused: the LDS-plane form handles 3-D programs'
-    return
-  if kernel_stream2d.rectangular(spec) and not req.rect:
-    req.lds_fields_note = ('not fused: a one-pass program with several outputs is fused only '
-                           'with fuse_outputs')
-    return
-  options = form_options('stream3d_lds', req.options)
-  shape = options.get('lds_shape')
-  found, error = first_fusable(spec, 1, [(kernel_stream3d_lds.emit, dict(
-      dict(zip(('waves', 'rows', 'lanes_x'), shape)) if shape else {}, fields=True))])
-  if found is None:
-    req.lds_fields_note = 'not fused: %s' % error
-    return
-  req.lds_fields_note = found[1]['name']
+  req.meta_notes[key] = found[1]['name']
   yield found
 
 
 # the kernel families in the order their kernels enter the table; each yields the
 # (text, entry) of the kernels it selects for this request and appends to `notes`
 FAMILIES = (fields2d_kernels, fields3d_kernels, fields1d_kernels, stream1d_kernels,
-            stream2d_kernels, stream3d_kernels, deep3d_kernels, lds3d_kernels,
-            lds3d_fields_kernels)
+            stream2d_kernels, stream3d_kernels, deep3d_kernels,
+            functools.partial(lds3d_kernels, LDS_PLANES),
+            functools.partial(lds3d_kernels, LDS_FIELDS))
 
 
 def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
@@ -967,8 +935,8 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   parts.append(text)
   notes = []
   req = Request(spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
-                fused_options, fuse_outputs=fuse_outputs, lds_planes=lds_planes,
-                lds_fields=lds_fields)
+                fused_options, dict(fuse_outputs=fuse_outputs, lds_planes=lds_planes,
+                                    lds_fields=lds_fields))
   for family in FAMILIES if fused else ():
     for ftext, entry in family(req, notes):
       parts.append(ftext)
@@ -978,10 +946,7 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
     parts.append(''.join('// %s\n' % n for n in notes))
   extra = dict(program_hash=kernel_common.program_hash(source),
                source_stages=[s['name'] for s in source['stages']])
-  if getattr(req, 'lds_note', None):
-    extra[LDS_PLANES_NOTE] = req.lds_note
-  if getattr(req, 'lds_fields_note', None):
-    extra[LDS_FIELDS_NOTE] = req.lds_fields_note
+  extra.update(req.meta_notes)
   parts.append(kernel_common.meta_symbol(spec, table, extra=extra))
   return '\n'.join(parts), table
 

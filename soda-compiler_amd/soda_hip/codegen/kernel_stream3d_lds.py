@@ -35,6 +35,8 @@ param[1 + j] carries output j's six extras, tiles and z chunks cover the union, 
 j stores a cell only inside j's box on all three axes.  An output that is one load at
 (0, 0, 0) of an input of its own type is stored straight from the window registers.
 """
+import types
+
 from . import spec as specmod
 from .kernel_common import builtin_type, cell_assignment, tensor_index
 from .kernel_fields3d import MAX_OUTPUTS
@@ -68,15 +70,35 @@ class Field:
     self.hy = (max([0] + [-r[1] for r in off]), max([0] + [r[1] for r in off]))
 
 
-def analyse(spec):
-  """(stage, [Field]) of a program in scope; NotFusable names what keeps it out."""
+def analyse(spec, fields=False):
+  """(stages, [Field]) of a program in scope; NotFusable names what keeps it out.  `fields`:
+  the scope of the form over several outputs, where a Field is the union of every stage's
+  reads of that input."""
   if spec['dim'] != 3:
     raise NotFusable('the LDS-plane form handles 3-D programs')
-  if len(spec['outputs']) != 1:
-    raise NotFusable('%d outputs: the LDS-plane form stores one' % len(spec['outputs']))
-  if len(spec['stages']) != 1:
-    raise NotFusable('%d stages: the LDS-plane form takes one stage, the output'
-                     % len(spec['stages']))
+  if fields:
+    if not 2 <= len(spec['outputs']) <= MAX_OUTPUTS:
+      raise NotFusable('%d outputs: the LDS-plane form over fields stores 2 to %d'
+                       % (len(spec['outputs']), MAX_OUTPUTS))
+    produced = [s['name'] for s in spec['stages']]
+    for stage in spec['stages']:
+      for name, _ in stage['loads']:
+        if name in produced:
+          raise NotFusable('stage %s reads stage %s: the LDS-plane form over fields takes '
+                           'stages that read inputs only' % (stage['name'], name))
+    if produced != list(spec['outputs']):
+      raise NotFusable('%d stages for %d outputs: the LDS-plane form over fields takes stages '
+                       'that are outputs' % (len(produced), len(spec['outputs'])))
+    if not (multi_field(spec) or rectangular(spec)):
+      raise NotFusable('iterate %d over %d input(s) and %d output(s) that do not feed each '
+                       'other pairwise' % (spec['iterate'], len(spec['inputs']),
+                                           len(spec['outputs'])))
+  else:
+    if len(spec['outputs']) != 1:
+      raise NotFusable('%d outputs: the LDS-plane form stores one' % len(spec['outputs']))
+    if len(spec['stages']) != 1:
+      raise NotFusable('%d stages: the LDS-plane form takes one stage, the output'
+                       % len(spec['stages']))
   types = specmod.tensor_c_types(spec)
   widths = sorted({specmod.ELEM_SIZE[t] for t in types.values()})
   if len(widths) > 1:
@@ -84,55 +106,21 @@ def analyse(spec):
   if widths[0] not in (4, 8):
     raise NotFusable('%d-byte elements: the LDS-plane form handles 4- and 8-byte ones'
                      % widths[0])
-  stage = spec['stages'][0]
-  fields = []
-  for t in spec['inputs']:
-    rels = [tuple(rel) for name, rel in stage['loads'] if name == t['name']]
-    if rels:
-      fields.append(Field(t['name'], t['c_type'], rels))
-  if not any(f.lds for f in fields):
-    raise NotFusable('no read off the z axis: nothing for an LDS plane to share')
-  return stage, fields
-
-
-def analyse_fields(spec):
-  """(stages, [Field]) of a program in the scope of the form over several outputs."""
-  if spec['dim'] != 3:
-    raise NotFusable('the LDS-plane form handles 3-D programs')
-  if not 2 <= len(spec['outputs']) <= MAX_OUTPUTS:
-    raise NotFusable('%d outputs: the LDS-plane form over fields stores 2 to %d'
-                     % (len(spec['outputs']), MAX_OUTPUTS))
-  produced = [s['name'] for s in spec['stages']]
-  for stage in spec['stages']:
-    for name, _ in stage['loads']:
-      if name in produced:
-        raise NotFusable('stage %s reads stage %s: the LDS-plane form over fields takes '
-                         'stages that read inputs only' % (stage['name'], name))
-  if produced != list(spec['outputs']):
-    raise NotFusable('%d stages for %d outputs: the LDS-plane form over fields takes stages '
-                     'that are outputs' % (len(produced), len(spec['outputs'])))
-  if not (multi_field(spec) or rectangular(spec)):
-    raise NotFusable('iterate %d over %d input(s) and %d output(s) that do not feed each '
-                     'other pairwise' % (spec['iterate'], len(spec['inputs']),
-                                         len(spec['outputs'])))
-  types = specmod.tensor_c_types(spec)
-  widths = sorted({specmod.ELEM_SIZE[t] for t in types.values()})
-  if len(widths) > 1:
-    raise NotFusable('mixed element widths')
-  if widths[0] not in (4, 8):
-    raise NotFusable('%d-byte elements: the LDS-plane form handles 4- and 8-byte ones'
-                     % widths[0])
-  fields = []
+  found = []
   for t in spec['inputs']:
     rels = []
     for stage in spec['stages']:
       rels += [tuple(rel) for name, rel in stage['loads']
                if name == t['name'] and tuple(rel) not in rels]
     if rels:
-      fields.append(Field(t['name'], t['c_type'], rels))
-  if not any(f.lds for f in fields):
+      found.append(Field(t['name'], t['c_type'], rels))
+  if not any(f.lds for f in found):
     raise NotFusable('no read off the z axis: nothing for an LDS plane to share')
-  return spec['stages'], fields
+  return spec['stages'], found
+
+
+def analyse_fields(spec):
+  return analyse(spec, fields=True)
 
 
 def passed_through(spec, stage):
@@ -194,7 +182,7 @@ def estimate_vgprs(fields, elem, geo, rows, computed=1):
 def shapes_by_loaded_cells(spec, shapes=SHAPES, fields=False):
   """The shapes ordered by cells loaded over cells stored, (TX + hx)(TY + hy) / (TX TY),
   least first (among equals as listed: more wavefronts, taller lanes first)."""
-  _, fields = analyse_fields(spec) if fields else analyse(spec)
+  _, fields = analyse(spec, fields)
   elem = specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
   return sorted(shapes, key=lambda s: geometry(fields, elem, *s)['loaded'])
 
@@ -216,6 +204,403 @@ def rotation(fields, max_period):
   return best[1], best[2]
 
 
+def fit(fields, elem, computed, shape, max_period, vgpr_budget):
+  """The figures of one shape - its geometry, estimated VGPRs and rotation - as the record
+  the printers share; NotFusable where it exceeds the LDS cap, the register budget or the
+  rotation period limit."""
+  k = types.SimpleNamespace(waves=shape[0], RW=shape[1], LX=shape[2],
+                            **geometry(fields, elem, *shape))
+  k.shape_text = '%d x %d tiles (%d wavefronts, %d rows per lane)' % (k.TX, k.TY, k.waves, k.RW)
+  if k.lds_bytes > LDS_CAP:
+    raise NotFusable('%s would need %d bytes of LDS (cap %d)' % (k.shape_text, k.lds_bytes,
+                                                                  LDS_CAP))
+  k.est_vgprs = estimate_vgprs(fields, elem, vars(k), k.RW, computed=computed)
+  if k.est_vgprs > vgpr_budget:
+    raise NotFusable('%s would need about %d VGPRs (budget %d)' % (k.shape_text, k.est_vgprs,
+                                                                    vgpr_budget))
+  k.period, k.slots = rotation(fields, max_period)
+  return k
+
+
+def first_fit(spec, several, fits):
+  """fits(shape) of the first of shapes_by_loaded_cells that it does not refuse; when all are
+  refused, the FIRST shape's error."""
+  error = None
+  for shape in shapes_by_loaded_cells(spec, fields=several):
+    try:
+      return fits(shape)
+    except NotFusable as e:
+      error = error or e
+  raise error
+
+
+def clamp(v, n):
+  """The index `v` clamped into [0, n - 1]."""
+  return '%s < 0 ? 0 : (%s > %s - 1 ? %s - 1 : %s)' % (v, v, n, n, v)
+
+
+def clamped_plane(expr):
+  return 'i64 zz = %s; zz = %s;' % (expr, clamp('zz', 'D'))
+
+
+def halo_guard(k, i):
+  """The guard of a work-item's i-th halo vector, where that may lie beyond the list."""
+  if (i + 1) * k.threads <= k.halo_vectors:
+    return ''
+  return 'if (tid + %d < %d) ' % (i * k.threads, k.halo_vectors)
+
+
+def lds_vector(field, row, vi):
+  """The vector `vi` of row `row`, relative to the lane's own, read from `field`'s plane."""
+  return 'l_%s_%s_%s' % (field, str(row).replace('-', 'm'), str(vi).replace('-', 'm'))
+
+
+def own(k, f, u, dz, r, c):
+  """The lane's own cell of plane z + dz at unrolled step u (z = the step's output plane;
+  the plane z + zhi + 1 is the one the step loads)."""
+  back = f.zhi + 1 - dz
+  assert 0 <= back < k.slots[f.name], (f.name, dz, back)
+  return 'w_%s[%d][%d][%d]' % (f.name, (u - back) % k.slots[f.name], r, c)
+
+
+def load_of(k, u, r, c):
+  """A stage's loads for the lane's cell (r, c) at step u: window registers, LDS vectors."""
+  def load(tensor, rel):
+    f = k.by_name[tensor]
+    dx, dy, dz = rel
+    if (dx, dy) == (0, 0):
+      return own(k, f, u, dz, r, c)
+    ry, vi, e = r + dy, (c + dx) // k.C, (c + dx) % k.C
+    if vi == 0 and 0 <= ry < k.RW:
+      return own(k, f, u, dz, ry, e)
+    return '%s[%d]' % (lds_vector(tensor, ry, vi), e)
+  return load
+
+
+def print_header(k, line):
+  """The comment that describes the kernel, and the vector types of its tensors."""
+  line('// fused depth-1 3-D kernel%s, LDS planes: %s, halo x %d+%d y %d+%d,'
+       % (k.over, k.shape_text, k.HXL, k.HXH, k.HYL, k.HYH))
+  line('// %d bytes of LDS, rotation period %d, %d planes walked before the first stored one, '
+       '~%d VGPRs' % (k.lds_bytes, k.period, k.fill, k.est_vgprs))
+  for f in k.fields:
+    line('//   %-12s z window [%d, %d] in %d register slots%s' % (
+        f.name, f.zlo, f.zhi, k.slots[f.name],
+        ', plane %+d in LDS' % f.zc if f.lds else ''))
+  for c_type in sorted({f.c_type for f in k.fields} | {st['c_type'] for st in k.stages}):
+    k.vec[c_type] = 'vec_%s_%s' % (k.name, c_type)
+    k.lvec[c_type] = 'lvec_%s_%s' % (k.name, c_type)
+    line('typedef %s %s __attribute__((ext_vector_type(%d), aligned(%d)));'
+         % (builtin_type(c_type), k.vec[c_type], k.C, k.elem))
+    line('typedef %s %s __attribute__((ext_vector_type(%d), aligned(16)));'
+         % (builtin_type(c_type), k.lvec[c_type], k.C))
+  if k.masks:
+    # which of its cells a lane stores does not change along the plane loop: hoisted out of
+    # it, each such condition would stay a 64-bit lane mask in a pair of SGPRs, for every
+    # row, column and output - more than the scalar file has.  Passed through an empty asm
+    # the lane's bits are opaque and the conditions are computed where they are used
+    # (kernel_fields3d: the same device)
+    line('template <typename T> DEV void %s_opaque(T& v) { asm volatile("" : "+v"(v)); }'
+         % k.name)
+
+
+def print_tile_prologue(k, line):
+  """The tile function up to its plane loop: addresses, clamped rows and columns, windows."""
+  C, RW, K = k.C, k.RW, k.K
+  line('template <bool INTERIOR>')
+  line('DEV void %s_tile(const soda_hip_args& a, %sconst i64 xs, const i64 ys, const i64 z0, '
+       'const i64 z1, const int tid%s) {' % (k.name, ''.join(
+           'const int %s, ' % m for m in k.masks), ''.join(
+           ', %s (*lds_%s)[%d][%d]' % (builtin_type(f.c_type), f.name, k.ROWS, k.PITCH)
+           for f in k.shared)))
+  line('  const i64 W = a.dims[0], H = a.dims[1], D = a.dims[2];')
+  line('  const i64 plane = W * H;')
+  line('  const int lx = tid %% %d, ly = tid / %d * %d;' % (k.LX, k.LX, RW))
+  line('  const i64 x = xs + lx * %d, y = ys + ly;' % C)
+  for f in k.fields:
+    T = builtin_type(f.c_type)
+    line('  const %s* __restrict__ g_%s = (const %s*)a.tensor[%d];' % (T, f.name, T,
+                                                                      k.index[f.name]))
+  for pointer, st in zip(k.out_pointers, k.stages):
+    T = builtin_type(st['c_type'])
+    line('  %s* __restrict__ %s = (%s*)a.tensor[%d];' % (T, pointer, T, k.index[st['name']]))
+  # the lane's own rows and columns, clamped into the array (what a clamp changes feeds only
+  # cells outside the box)
+  line('  i64 row_off[%d], col[%d];' % (RW, C))
+  for r in range(RW):
+    line('  { i64 yy = y + %d; if (!INTERIOR) yy = %s; row_off[%d] = yy * W; }'
+         % (r, clamp('yy', 'H'), r))
+  for c in range(C):
+    line('  { i64 xx = x + %d; if (!INTERIOR) xx = %s; col[%d] = xx; }'
+         % (c, clamp('xx', 'W'), c))
+  # the halo vectors this work-item fetches: where each lies in a slot and in a plane.  The
+  # halo ring of a slot as a list of vectors: the rows above and below at full pitch, then
+  # the vectors left and right of the tile's own rows
+  PV, TXV, HXLV, SV = k.PITCH // C, k.TX // C, k.HXL // C, (k.HXL + k.HXH) // C
+  NTB = (k.HYL + k.HYH) * PV
+  assert k.halo_vectors == NTB + k.TY * SV
+  line('  int h_lds[%d]; i64 h_row[%d], h_x[%d];' % (K, K, K))
+  for i in range(K):
+    line('  {')
+    line('    const int idx = tid + %d;' % (i * k.threads))
+    line('    int row, vcol;')
+    top = 'const int rh = idx / %d; vcol = idx %% %d; row = rh < %d ? rh : rh + %d;' % (
+        PV, PV, k.HYL, k.TY)
+    side = 'const int j = idx - %d; row = %d + j / %d; const int sv = j %% %d; ' \
+        'vcol = sv < %d ? sv : sv + %d;' % (NTB, k.HYL, max(SV, 1), max(SV, 1), HXLV, TXV)
+    if NTB and SV:
+      line('    if (idx < %d) { %s } else { %s }' % (NTB, top, side))
+    else:
+      line('    { %s }' % (top if NTB else side))
+    # (a work-item beyond the list keeps a position inside the slot and the plane: it
+    # neither loads nor writes, the guard is `tid + k * threads < vectors`)
+    line('    if (idx >= %d) { row = 0; vcol = 0; }' % k.halo_vectors)
+    line('    h_lds[%d] = row * %d + vcol * %d;' % (i, k.PITCH, C))
+    line('    i64 yy = ys - %d + row; if (!INTERIOR) yy = %s;' % (k.HYL, clamp('yy', 'H')))
+    line('    h_row[%d] = yy * W; h_x[%d] = xs - %d + vcol * %d;' % (i, i, k.HXL, C))
+    line('  }')
+  for f in k.fields:
+    line('  %s w_%s[%d][%d][%d];' % (builtin_type(f.c_type), f.name, k.slots[f.name], RW, C))
+    for s in range(k.slots[f.name]):
+      for r in range(RW):
+        line('  ' + ' '.join('w_%s[%d][%d][%d] = 0;' % (f.name, s, r, c) for c in range(C)))
+  line('  const i64 steps = (z1 - z0) + %d;' % k.fill)
+  line('  for (i64 n = 0; n < steps; n += %d) {' % k.period)
+
+
+def print_loads_ahead(k, line, u):
+  """Every input's own cells of the plane after its window, into the window's free slot."""
+  for f in k.fields:
+    T, V = builtin_type(f.c_type), k.vec[f.c_type]
+    line('      {  // own cells of plane z%+d of %s, one plane ahead' % (f.zhi + 1, f.name))
+    line('        %s' % clamped_plane('z + %d' % (f.zhi + 1)))
+    line('        const %s* p = g_%s + zz * plane;' % (T, f.name))
+    for r in range(k.RW):
+      cells = [own(k, f, u, f.zhi + 1, r, c) for c in range(k.C)]
+      line('        if (INTERIOR) { const %s v = *(const %s*)(p + row_off[%d] + x);%s }' % (
+          V, V, r, ''.join(' %s = v[%d];' % (cell, c) for c, cell in enumerate(cells))))
+      line('        else {%s }' % ''.join(' %s = p[row_off[%d] + col[%d]];' % (cell, r, c)
+                                         for c, cell in enumerate(cells)))
+    line('      }')
+
+
+def print_halo_fetch(k, line):
+  """The halo ring of the plane the step's LDS fill writes, into registers."""
+  for f in k.shared:
+    T, V = builtin_type(f.c_type), k.vec[f.c_type]
+    line('      %s halo_%s[%d];' % (k.lvec[f.c_type], f.name, k.K))
+    line('      {  // halo ring of plane z%+d of %s' % (f.zc + 1, f.name))
+    line('        %s' % clamped_plane('z + %d' % (f.zc + 1)))
+    line('        const %s* p = g_%s + zz * plane;' % (T, f.name))
+    for i in range(k.K):
+      line('        halo_%s[%d] = 0;' % (f.name, i))
+      line('        %s{' % halo_guard(k, i))
+      line('          if (INTERIOR) { const %s v = *(const %s*)(p + h_row[%d] + h_x[%d]);%s }' % (
+          V, V, i, i,
+          ''.join(' halo_%s[%d][%d] = v[%d];' % (f.name, i, c, c) for c in range(k.C))))
+      line('          else {%s }' % ''.join(
+          ' { i64 xx = h_x[%d] + %d; xx = %s; halo_%s[%d][%d] = p[h_row[%d] + xx]; }'
+          % (i, c, clamp('xx', 'W'), f.name, i, c, i) for c in range(k.C)))
+      line('        }')
+    line('      }')
+
+
+def print_lds_reads(k, line, u):
+  """The in-plane neighbours of the lane's cells, as whole vectors from the slot u % 2."""
+  for fname, ry, vi in lds_vectors(k.fields, k.C, k.RW):
+    V = k.lvec[k.by_name[fname].c_type]
+    line('        const %s %s = *(const %s*)&lds_%s[%d][%d + ly + %d][%d + lx * %d + %d];'
+         % (V, lds_vector(fname, ry, vi), V, fname, u % 2, k.HYL, ry, k.HXL, k.C, vi * k.C))
+
+
+def print_compute(k, line, stage, u, indent):
+  """The lane's RW x C cells of one stage, into out_cells."""
+  line('%s%s out_cells[%d][%d];' % (indent, builtin_type(stage['c_type']), k.RW, k.C))
+  for r in range(k.RW):
+    for c in range(k.C):
+      cell_assignment(stage, 'out_cells[%d][%d]' % (r, c), load_of(k, u, r, c), line, indent)
+
+
+def store_in_launch_box(k, line, u):
+  """One output, stored inside the launch's box a.box_lo/hi."""
+  stage, = k.stages
+  T, V, C = builtin_type(stage['c_type']), k.vec[stage['c_type']], k.C
+  print_compute(k, line, stage, u, '        ')
+  line('        %s* q = %s + z * plane;' % (T, k.out_pointers[0]))
+  for r in range(k.RW):
+    line('        if (y + %d >= a.box_lo[1] && y + %d < a.box_hi[1]) {' % (r, r))
+    line('          if (x >= a.box_lo[0] && x + %d <= a.box_hi[0]) {' % C)
+    line('            %s v;%s *(%s*)(q + row_off[%d] + x) = v;' % (
+        V, ''.join(' v[%d] = out_cells[%d][%d];' % (c, r, c) for c in range(C)), V, r))
+    line('          } else {')
+    for c in range(C):
+      line('            if (x + %d >= a.box_lo[0] && x + %d < a.box_hi[0]) '
+           'q[row_off[%d] + x + %d] = out_cells[%d][%d];' % (c, c, r, c, r, c))
+    line('          }')
+    line('        }')
+
+
+def store_in_own_boxes(k, line, u):
+  """Several outputs, each inside its own box: the lane masks cells<j>, sn_lo<j>, sn_hi<j>."""
+  C = k.C
+  line('        const int m = (int)n + %d;' % u)
+  for j, st in enumerate(k.stages):
+    T, V = builtin_type(st['c_type']), k.vec[st['c_type']]
+    line('        int mine%d = m >= sn_lo%d && m < sn_hi%d ? cells%d : 0; %s_opaque(mine%d);'
+         % (j, j, j, j, k.name, j))
+    line('        if (mine%d) {  // %s' % (j, st['name']))
+    if k.through[j] is None:
+      print_compute(k, line, st, u, '          ')
+      cell = lambda r, c: 'out_cells[%d][%d]' % (r, c)
+    else:     # handed on: the lane's own cells of plane z, as they lie in the window
+      cell = lambda r, c, f=k.by_name[k.through[j]]: own(k, f, u, 0, r, c)
+    line('          %s* q = %s + z * plane;' % (T, k.out_pointers[j]))
+    for r in range(k.RW):
+      whole = ((1 << C) - 1) << (r * C)
+      line('          if (mine%d & %d) {' % (j, whole))
+      line('            if ((mine%d & %d) == %d) {' % (j, whole, whole))
+      line('              %s v;%s *(%s*)(q + row_off[%d] + x) = v;' % (
+          V, ''.join(' v[%d] = %s;' % (c, cell(r, c)) for c in range(C)), V, r))
+      line('            } else {')
+      for c in range(C):
+        line('              if (mine%d & %d) q[row_off[%d] + x + %d] = %s;' % (
+            j, 1 << (r * C + c), r, c, cell(r, c)))
+      line('            }')
+      line('          }')
+    line('        }')
+
+
+def print_lds_fill(k, line, u):
+  """The other slot gets the next step's plane: own cells from the window, halo ring."""
+  for f in k.shared:
+    V = k.lvec[f.c_type]
+    for r in range(k.RW):
+      line('      { %s v;%s *(%s*)&lds_%s[%d][%d + ly + %d][%d + lx * %d] = v; }' % (
+          V, ''.join(' v[%d] = %s;' % (c, own(k, f, u, f.zc + 1, r, c)) for c in range(k.C)),
+          V, f.name, (u + 1) % 2, k.HYL, r, k.HXL, k.C))
+    for i in range(k.K):
+      line('      %s*(%s*)(&lds_%s[%d][0][0] + h_lds[%d]) = halo_%s[%d];' % (
+          halo_guard(k, i), V, f.name, (u + 1) % 2, i, f.name, i))
+
+
+def print_step(k, line, u, store):
+  """One unrolled step of the plane loop; `store` prints what it computes and stores."""
+  line('    {  // unrolled step %d: output plane z, slot %d read, slot %d filled' % (
+      u, u % 2, (u + 1) % 2))
+  if u:
+    line('      if (n + %d >= steps) break;' % u)      # the whole workgroup leaves together
+  line('      const i64 z = z0 + n + %d;' % (u - k.fill))
+  print_loads_ahead(k, line, u)
+  print_halo_fetch(k, line)
+  # compute: every step from the first one whose window is complete
+  line('      if (n + %d >= %d) {' % (u, k.fill))
+  print_lds_reads(k, line, u)
+  store(k, line, u)
+  line('      }')
+  print_lds_fill(k, line, u)
+  line('      soda_block_barrier();')
+  line('    }')
+
+
+def print_origin_and_chunk(k, line, lo, hi):
+  """The workgroup's tile and z chunk of the box [lo, hi)."""
+  line('  const i64 x_origin = %s - %s %% %d;' % (lo[0], lo[0], k.C))
+  line('  const i64 xs = x_origin + (i64)__builtin_amdgcn_workgroup_id_x() * %d;' % k.TX)
+  line('  const i64 ys = %s + (i64)__builtin_amdgcn_workgroup_id_y() * %d;' % (lo[1], k.TY))
+  line('  const i64 chunk = a.param[0] > 0 ? a.param[0] : %d;' % k.chunk_planes)
+  line('  const i64 z0 = %s + (i64)__builtin_amdgcn_workgroup_id_z() * chunk;' % lo[2])
+  # (the same for every work-item of the workgroup: nobody waits at a barrier for them)
+  line('  if (xs >= %s || ys >= %s || z0 >= %s) return;' % tuple(hi))
+  line('  const i64 z1 = z0 + chunk < %s ? z0 + chunk : %s;' % (hi[2], hi[2]))
+
+
+def entry_over_launch_box(k, line):
+  """One output: tiles and chunks cover the launch's box."""
+  print_origin_and_chunk(k, line, ['a.box_lo[%d]' % d for d in range(3)],
+                         ['a.box_hi[%d]' % d for d in range(3)])
+
+
+def entry_over_own_boxes(k, line):
+  """Several outputs: tiles and chunks cover the union of their boxes; the lane masks."""
+  C = k.C
+  n_out = len(k.stages)
+  # the union of the outputs' boxes is what tiles and chunks cover (the launcher sizes
+  # the grid by the same rule: csrc/schedule.cpp, make_launch)
+  for d in range(3):
+    for side, shift, sign in (('lo', 8 * d, '-'), ('hi', 24 + 8 * d, '+')):
+      line('  i64 %s%d = 0;' % (side, d))
+      for j in range(n_out):
+        line('  { const i64 e = (a.param[%d] >> %d) & 255; if (e > %s%d) %s%d = e; }'
+             % (1 + j, shift, side, d, side, d))
+      line('  %s%d = a.box_%s[%d] %s %s%d;' % (side, d, side, d, sign, side, d))
+  print_origin_and_chunk(k, line, ['lo%d' % d for d in range(3)],
+                         ['hi%d' % d for d in range(3)])
+
+  # the box of output j: the launch's box widened by the extras of param[1 + j], each
+  # bound computed where it is used (eighteen 64-bit bounds kept would fill the scalar file)
+  box_lo = lambda j, d: '(a.box_lo[%d] - ((a.param[%d] >> %d) & 255))' % (d, 1 + j, 8 * d)
+  box_hi = lambda j, d: '(a.box_hi[%d] + ((a.param[%d] >> %d) & 255))' % (d, 1 + j,
+                                                                         24 + 8 * d)
+
+  def within(what, first, size):
+    """`what` as a distance from `first`, clamped into [0, size]"""
+    return '(int)(%s - %s < 0 ? 0 : %s - %s > %s ? %s : %s - %s)' % (
+        what, first, what, first, size, size, what, first)
+
+  line('  const int lx = tid %% %d, ly = tid / %d * %d;' % (k.LX, k.LX, k.RW))
+  for j in range(n_out):
+    # what output j stores of this tile and chunk, worked out here, once for both paths, and
+    # kept in three VECTOR registers per output (the one-output form leaves a dozen scalar
+    # registers free, fewer than the bounds of three boxes).  Columns and rows: which of
+    # the lane's own cells lie in j's box, bit r * C + c.  Planes: the steps of the plane
+    # loop that compute them (step m computes plane z0 + m - fill)
+    line('  int cells%d = 0;' % j)
+    line('  {')
+    line('    const int sx_lo = %s, sx_hi = %s;' % (within(box_lo(j, 0), 'xs', k.TX),
+                                                  within(box_hi(j, 0), 'xs', k.TX)))
+    line('    const int sy_lo = %s, sy_hi = %s;' % (within(box_lo(j, 1), 'ys', k.TY),
+                                                  within(box_hi(j, 1), 'ys', k.TY)))
+    for r in range(k.RW):
+      line('    if (ly + %d >= sy_lo && ly + %d < sy_hi) {%s }' % (r, r, ''.join(
+          ' if (lx * %d + %d >= sx_lo && lx * %d + %d < sx_hi) cells%d |= %d;'
+          % (C, c, C, c, j, 1 << (r * C + c)) for c in range(C))))
+    line('  }')
+    line('  int sn_lo%d = %s + %d, sn_hi%d = %s + %d;' % (
+        j, within(box_lo(j, 2), 'z0', '(z1 - z0)'), k.fill,
+        j, within(box_hi(j, 2), 'z0', '(z1 - z0)'), k.fill))
+    line('  %s_opaque(cells%d); %s_opaque(sn_lo%d); %s_opaque(sn_hi%d);'
+         % (k.name, j, k.name, j, k.name, j))
+
+
+def print_entry(k, line, prologue):
+  """The entry kernel: LDS slots, tile and chunk (`prologue`), the interior or the edge path."""
+  line('GLOBAL WG_SIZE(%d) void %s(soda_hip_args a) {' % (k.threads, k.name))
+  for f in k.shared:
+    line('  __attribute__((shared, aligned(16))) %s lds_%s[2][%d][%d];' % (
+        builtin_type(f.c_type), f.name, k.ROWS, k.PITCH))
+  line('  const int tid = __builtin_amdgcn_workitem_id_x();')
+  prologue(k, line)
+  line('  const bool interior = xs - %d >= 0 && xs + %d <= a.dims[0] && '
+       'ys - %d >= 0 && ys + %d <= a.dims[1];' % (k.HXL, k.TX + k.HXH, k.HYL, k.TY + k.HYH))
+  args = 'a, %sxs, ys, z0, z1, tid%s' % (''.join('%s, ' % m for m in k.masks),
+                                        ''.join(', lds_%s' % f.name for f in k.shared))
+  line('  if (interior) %s_tile<true>(%s);' % (k.name, args))
+  line('  else %s_tile<false>(%s);' % (k.name, args))
+  line('}')
+
+
+def table_entry(k):
+  loaded = len(k.shared) * k.ROWS * k.PITCH + (len(k.fields) - len(k.shared)) * k.TX * k.TY
+  entry = dict(name=k.name, kind='fused', depth=1, stage=-1, block=[k.threads, 1, 1],
+               tile=[k.TX, k.TY, k.chunk_planes, 1], origin_align=k.C, fill_rows=k.fill,
+               cols=k.C, rows=k.RW, w_out=k.TX, r_out=k.TY, period=k.period,
+               est_vgprs=k.est_vgprs, lds_bytes=k.lds_bytes, lds_planes=len(k.shared),
+               waves=k.waves, halo=[k.HXL, k.HXH, k.HYL, k.HYH], loaded_cells=loaded)
+  if k.masks:
+    entry['fields'] = len(k.stages)
+  return entry
+
+
 def emit(spec, depth=1, waves=None, rows=None, lanes_x=None, chunk_planes=64,
          max_period=16, vgpr_budget=250, fields=False):
   """Returns (text, kernel table entry).  Without a shape: the first of
@@ -224,350 +609,34 @@ def emit(spec, depth=1, waves=None, rows=None, lanes_x=None, chunk_planes=64,
   if depth != 1:
     raise NotFusable('the LDS-plane form is depth 1')
   several = bool(fields)
-  if several:
-    stages, fields = analyse_fields(spec)
-  else:
-    stage, fields = analyse(spec)
-    stages = [stage]
-  types = specmod.tensor_c_types(spec)
-  index = tensor_index(spec)
-  out_name = spec['outputs'][0]
-  elem = specmod.ELEM_SIZE[types[out_name]]
+  stages, fields = analyse(spec, several)
+  elem = specmod.ELEM_SIZE[specmod.tensor_c_types(spec)[spec['outputs'][0]]]
   # per output, the input it hands on unchanged (stored from the window, no cells of its own)
   through = [passed_through(spec, st) if several else None for st in stages]
-  if waves is None:
-    error = None
-    for shape in shapes_by_loaded_cells(spec, fields=several):
-      try:
-        return emit(spec, depth, *shape, chunk_planes=chunk_planes, max_period=max_period,
-                    vgpr_budget=vgpr_budget, fields=several)
-      except NotFusable as e:
-        error = error or e
-    raise error
-  geo = geometry(fields, elem, waves, rows, lanes_x)
-  C, RW, LX, NT = geo['C'], rows, lanes_x, geo['threads']
-  TX, TY, HXL, HXH, HYL, HYH = (geo[k] for k in ('TX', 'TY', 'HXL', 'HXH', 'HYL', 'HYH'))
-  PITCH, ROWS = geo['PITCH'], geo['ROWS']
-  shape_text = '%d x %d tiles (%d wavefronts, %d rows per lane)' % (TX, TY, waves, RW)
-  if geo['lds_bytes'] > LDS_CAP:
-    raise NotFusable('%s would need %d bytes of LDS (cap %d)' % (shape_text, geo['lds_bytes'],
-                                                                  LDS_CAP))
-  est_vgprs = estimate_vgprs(fields, elem, geo, RW, computed=through.count(None))
-  if est_vgprs > vgpr_budget:
-    raise NotFusable('%s would need about %d VGPRs (budget %d)' % (shape_text, est_vgprs,
-                                                                    vgpr_budget))
-  period, slots = rotation(fields, max_period)
-  fill = max(f.zhi - f.zlo + 1 for f in fields)
-  shared = [f for f in fields if f.lds]
-  name = kernel_name(spec, several)
-  T_out = builtin_type(types[out_name])
+  fits = lambda shape: fit(fields, elem, through.count(None), shape, max_period, vgpr_budget)
+  k = first_fit(spec, several, fits) if waves is None else fits((waves, rows, lanes_x))
+  k.name, k.stages, k.fields, k.through = kernel_name(spec, several), stages, fields, through
+  k.shared, k.by_name = [f for f in fields if f.lds], {f.name: f for f in fields}
+  k.index, k.elem, k.chunk_planes = tensor_index(spec), elem, chunk_planes
+  k.fill = max(f.zhi - f.zlo + 1 for f in fields)
+  k.K = -(-k.halo_vectors // k.threads)
+  k.vec, k.lvec = {}, {}
+  assert k.halo_vectors > 0
+  # what differs between the two forms, as data: the header's remark, the output pointers of
+  # the tile function and the lane masks the entry kernel hands it (none for one output)
   n_out = len(stages)
-  # the halo ring of a slot as a list of vectors: the rows above and below at full pitch,
-  # then the vectors left and right of the tile's own rows
-  PV, TXV, HXLV, SV = PITCH // C, TX // C, HXL // C, (HXL + HXH) // C
-  NTB, NH = (HYL + HYH) * PV, geo['halo_vectors']
-  assert NH == NTB + TY * SV and NH > 0
-  K = -(-NH // NT)
-  by_name = {f.name: f for f in fields}
+  k.over = ' over %d outputs' % n_out if several else ''
+  k.out_pointers = ['g_out%d' % j for j in range(n_out)] if several else ['g_out']
+  k.masks = ['%s%d' % (m, j) for j in range(n_out if several else 0)
+             for m in ('cells', 'sn_lo', 'sn_hi')]
+  store = store_in_own_boxes if several else store_in_launch_box
+  prologue = entry_over_own_boxes if several else entry_over_launch_box
 
   o = []
-  line = o.append
-  line('// fused depth-1 3-D kernel%s, LDS planes: %s, halo x %d+%d y %d+%d,'
-       % (' over %d outputs' % n_out if several else '', shape_text, HXL, HXH, HYL, HYH))
-  line('// %d bytes of LDS, rotation period %d, %d planes walked before the first stored one, '
-       '~%d VGPRs' % (geo['lds_bytes'], period, fill, est_vgprs))
-  for f in fields:
-    line('//   %-12s z window [%d, %d] in %d register slots%s' % (
-        f.name, f.zlo, f.zhi, slots[f.name],
-        ', plane %+d in LDS' % f.zc if f.lds else ''))
-  vec, lvec = {}, {}
-  for c_type in sorted({f.c_type for f in fields} | {st['c_type'] for st in stages}):
-    vec[c_type] = 'vec_%s_%s' % (name, c_type)
-    lvec[c_type] = 'lvec_%s_%s' % (name, c_type)
-    line('typedef %s %s __attribute__((ext_vector_type(%d), aligned(%d)));'
-         % (builtin_type(c_type), vec[c_type], C, elem))
-    line('typedef %s %s __attribute__((ext_vector_type(%d), aligned(16)));'
-         % (builtin_type(c_type), lvec[c_type], C))
-  if several:
-    # which of its cells a lane stores does not change along the plane loop: hoisted out of
-    # it, each such condition would stay a 64-bit lane mask in a pair of SGPRs, for every
-    # row, column and output - more than the scalar file has.  Passed through an empty asm
-    # the lane's bits are opaque and the conditions are computed where they are used
-    # (kernel_fields3d: the same device)
-    line('template <typename T> DEV void %s_opaque(T& v) { asm volatile("" : "+v"(v)); }'
-         % name)
-  line('template <bool INTERIOR>')
-  line('DEV void %s_tile(const soda_hip_args& a, %sconst i64 xs, const i64 ys, const i64 z0, '
-       'const i64 z1, const int tid%s) {' % (name, ''.join(
-           'const int cells%d, const int sn_lo%d, const int sn_hi%d, ' % (j, j, j)
-           for j in range(n_out if several else 0)), ''.join(
-           ', %s (*lds_%s)[%d][%d]' % (builtin_type(f.c_type), f.name, ROWS, PITCH)
-           for f in shared)))
-  line('  const i64 W = a.dims[0], H = a.dims[1], D = a.dims[2];')
-  line('  const i64 plane = W * H;')
-  line('  const int lx = tid %% %d, ly = tid / %d * %d;' % (LX, LX, RW))
-  line('  const i64 x = xs + lx * %d, y = ys + ly;' % C)
-  for f in fields:
-    T = builtin_type(f.c_type)
-    line('  const %s* __restrict__ g_%s = (const %s*)a.tensor[%d];' % (T, f.name, T,
-                                                                      index[f.name]))
-  if not several:
-    line('  %s* __restrict__ g_out = (%s*)a.tensor[%d];' % (T_out, T_out, index[out_name]))
-  for j, st in enumerate(stages if several else ()):
-    T = builtin_type(st['c_type'])
-    line('  %s* __restrict__ g_out%d = (%s*)a.tensor[%d];' % (T, j, T, index[st['name']]))
-  # the lane's own rows and columns, clamped into the array (what a clamp changes feeds only
-  # cells outside the box)
-  line('  i64 row_off[%d], col[%d];' % (RW, C))
-  for r in range(RW):
-    line('  { i64 yy = y + %d; if (!INTERIOR) yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy); '
-         'row_off[%d] = yy * W; }' % (r, r))
-  for c in range(C):
-    line('  { i64 xx = x + %d; if (!INTERIOR) xx = xx < 0 ? 0 : (xx > W - 1 ? W - 1 : xx); '
-         'col[%d] = xx; }' % (c, c))
-  # the halo vectors this work-item fetches: where each lies in a slot and in a plane
-  line('  int h_lds[%d]; i64 h_row[%d], h_x[%d];' % (K, K, K))
-  for k in range(K):
-    line('  {')
-    line('    const int idx = tid + %d;' % (k * NT))
-    line('    int row, vcol;')
-    top = 'const int rh = idx / %d; vcol = idx %% %d; row = rh < %d ? rh : rh + %d;' % (
-        PV, PV, HYL, TY)
-    side = 'const int j = idx - %d; row = %d + j / %d; const int sv = j %% %d; ' \
-        'vcol = sv < %d ? sv : sv + %d;' % (NTB, HYL, max(SV, 1), max(SV, 1), HXLV, TXV)
-    if NTB and SV:
-      line('    if (idx < %d) { %s } else { %s }' % (NTB, top, side))
-    else:
-      line('    { %s }' % (top if NTB else side))
-    # (a work-item beyond the list keeps a position inside the slot and the plane: it
-    # neither loads nor writes, the guard is `tid + k * threads < vectors`)
-    line('    if (idx >= %d) { row = 0; vcol = 0; }' % NH)
-    line('    h_lds[%d] = row * %d + vcol * %d;' % (k, PITCH, C))
-    line('    i64 yy = ys - %d + row; if (!INTERIOR) yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy);'
-         % HYL)
-    line('    h_row[%d] = yy * W; h_x[%d] = xs - %d + vcol * %d;' % (k, k, HXL, C))
-    line('  }')
-  for f in fields:
-    T = builtin_type(f.c_type)
-    line('  %s w_%s[%d][%d][%d];' % (T, f.name, slots[f.name], RW, C))
-    for s in range(slots[f.name]):
-      for r in range(RW):
-        line('  ' + ' '.join('w_%s[%d][%d][%d] = 0;' % (f.name, s, r, c) for c in range(C)))
-  line('  const i64 steps = (z1 - z0) + %d;' % fill)
-  line('  for (i64 n = 0; n < steps; n += %d) {' % period)
-
-  def own(f, u, dz, r, c):
-    """The lane's own cell of plane z + dz at unrolled step u (z = the step's output plane;
-    the plane z + zhi + 1 is the one the step loads)."""
-    back = f.zhi + 1 - dz
-    assert 0 <= back < slots[f.name], (f.name, dz, back)
-    return 'w_%s[%d][%d][%d]' % (f.name, (u - back) % slots[f.name], r, c)
-
-  def clamped_plane(expr):
-    return 'i64 zz = %s; zz = zz < 0 ? 0 : (zz > D - 1 ? D - 1 : zz);' % expr
-
-  for u in range(period):
-    line('    {  // unrolled step %d: output plane z, slot %d read, slot %d filled' % (
-        u, u % 2, (u + 1) % 2))
-    if u:
-      line('      if (n + %d >= steps) break;' % u)      # the whole workgroup leaves together
-    line('      const i64 z = z0 + n + %d;' % (u - fill))
-    for f in fields:
-      T = builtin_type(f.c_type)
-      line('      {  // own cells of plane z%+d of %s, one plane ahead' % (f.zhi + 1, f.name))
-      line('        %s' % clamped_plane('z + %d' % (f.zhi + 1)))
-      line('        const %s* p = g_%s + zz * plane;' % (T, f.name))
-      for r in range(RW):
-        cells = [own(f, u, f.zhi + 1, r, c) for c in range(C)]
-        line('        if (INTERIOR) { const %s v = *(const %s*)(p + row_off[%d] + x);%s }' % (
-            vec[f.c_type], vec[f.c_type], r,
-            ''.join(' %s = v[%d];' % (cell, c) for c, cell in enumerate(cells))))
-        line('        else {%s }' % ''.join(' %s = p[row_off[%d] + col[%d]];' % (cell, r, c)
-                                           for c, cell in enumerate(cells)))
-      line('      }')
-    for f in shared:
-      T = builtin_type(f.c_type)
-      line('      %s halo_%s[%d];' % (lvec[f.c_type], f.name, K))
-      line('      {  // halo ring of plane z%+d of %s' % (f.zc + 1, f.name))
-      line('        %s' % clamped_plane('z + %d' % (f.zc + 1)))
-      line('        const %s* p = g_%s + zz * plane;' % (T, f.name))
-      for k in range(K):
-        guard = '' if (k + 1) * NT <= NH else 'if (tid + %d < %d) ' % (k * NT, NH)
-        line('        halo_%s[%d] = 0;' % (f.name, k))
-        line('        %s{' % guard)
-        line('          if (INTERIOR) { const %s v = *(const %s*)(p + h_row[%d] + h_x[%d]);%s }' % (
-            vec[f.c_type], vec[f.c_type], k, k,
-            ''.join(' halo_%s[%d][%d] = v[%d];' % (f.name, k, c, c) for c in range(C))))
-        line('          else {%s }' % ''.join(
-            ' { i64 xx = h_x[%d] + %d; xx = xx < 0 ? 0 : (xx > W - 1 ? W - 1 : xx); '
-            'halo_%s[%d][%d] = p[h_row[%d] + xx]; }' % (k, c, f.name, k, c, k)
-            for c in range(C)))
-        line('        }')
-      line('      }')
-    # compute: every step from the first one whose window is complete
-    line('      if (n + %d >= %d) {' % (u, fill))
-    wanted = lds_vectors(fields, C, RW)
-    for fname, ry, vi in wanted:
-      f = by_name[fname]
-      line('        const %s l_%s_%s_%s = *(const %s*)&lds_%s[%d][%d + ly + %d][%d + lx * %d + %d];'
-           % (lvec[f.c_type], fname, str(ry).replace('-', 'm'), str(vi).replace('-', 'm'),
-              lvec[f.c_type], fname, u % 2, HYL, ry, HXL, C, vi * C))
-    def load_of(u, r, c):
-      def load(tensor, rel):
-        f = by_name[tensor]
-        dx, dy, dz = rel
-        if (dx, dy) == (0, 0):
-          return own(f, u, dz, r, c)
-        ry, vi, e = r + dy, (c + dx) // C, (c + dx) % C
-        if vi == 0 and 0 <= ry < RW:
-          return own(f, u, dz, ry, e)
-        return 'l_%s_%s_%s[%d]' % (tensor, str(ry).replace('-', 'm'),
-                                   str(vi).replace('-', 'm'), e)
-      return load
-
-    if not several:
-      line('        %s out_cells[%d][%d];' % (T_out, RW, C))
-      for r in range(RW):
-        for c in range(C):
-          cell_assignment(stage, 'out_cells[%d][%d]' % (r, c), load_of(u, r, c), line,
-                          '        ')
-      line('        %s* q = g_out + z * plane;' % T_out)
-      for r in range(RW):
-        line('        if (y + %d >= a.box_lo[1] && y + %d < a.box_hi[1]) {' % (r, r))
-        line('          if (x >= a.box_lo[0] && x + %d <= a.box_hi[0]) {' % C)
-        line('            %s v;%s *(%s*)(q + row_off[%d] + x) = v;' % (
-            vec[types[out_name]], ''.join(' v[%d] = out_cells[%d][%d];' % (c, r, c)
-                                          for c in range(C)), vec[types[out_name]], r))
-        line('          } else {')
-        for c in range(C):
-          line('            if (x + %d >= a.box_lo[0] && x + %d < a.box_hi[0]) '
-               'q[row_off[%d] + x + %d] = out_cells[%d][%d];' % (c, c, r, c, r, c))
-        line('          }')
-        line('        }')
-    if several:
-      line('        const int m = (int)n + %d;' % u)
-    for j, st in enumerate(stages if several else ()):
-      # output j: the planes, rows and columns of its own box
-      T, V = builtin_type(st['c_type']), vec[st['c_type']]
-      line('        int mine%d = m >= sn_lo%d && m < sn_hi%d ? cells%d : 0; %s_opaque(mine%d);'
-           % (j, j, j, j, name, j))
-      line('        if (mine%d) {  // %s' % (j, st['name']))
-      if through[j] is None:
-        line('          %s out_cells[%d][%d];' % (T, RW, C))
-        for r in range(RW):
-          for c in range(C):
-            cell_assignment(st, 'out_cells[%d][%d]' % (r, c), load_of(u, r, c), line,
-                            '          ')
-        cell = lambda r, c: 'out_cells[%d][%d]' % (r, c)
-      else:     # handed on: the lane's own cells of plane z, as they lie in the window
-        cell = lambda r, c, f=by_name[through[j]], u=u: own(f, u, 0, r, c)
-      line('          %s* q = g_out%d + z * plane;' % (T, j))
-      for r in range(RW):
-        whole = ((1 << C) - 1) << (r * C)
-        line('          if (mine%d & %d) {' % (j, whole))
-        line('            if ((mine%d & %d) == %d) {' % (j, whole, whole))
-        line('              %s v;%s *(%s*)(q + row_off[%d] + x) = v;' % (
-            V, ''.join(' v[%d] = %s;' % (c, cell(r, c)) for c in range(C)), V, r))
-        line('            } else {')
-        for c in range(C):
-          line('              if (mine%d & %d) q[row_off[%d] + x + %d] = %s;' % (
-              j, 1 << (r * C + c), r, c, cell(r, c)))
-        line('            }')
-        line('          }')
-      line('        }')
-    line('      }')
-    # the other slot gets the next step's plane: own cells from the window, halo ring
-    for f in shared:
-      for r in range(RW):
-        line('      { %s v;%s *(%s*)&lds_%s[%d][%d + ly + %d][%d + lx * %d] = v; }' % (
-            lvec[f.c_type], ''.join(' v[%d] = %s;' % (c, own(f, u, f.zc + 1, r, c))
-                                    for c in range(C)),
-            lvec[f.c_type], f.name, (u + 1) % 2, HYL, r, HXL, C))
-      for k in range(K):
-        guard = '' if (k + 1) * NT <= NH else 'if (tid + %d < %d) ' % (k * NT, NH)
-        line('      %s*(%s*)(&lds_%s[%d][0][0] + h_lds[%d]) = halo_%s[%d];' % (
-            guard, lvec[f.c_type], f.name, (u + 1) % 2, k, f.name, k))
-    line('      soda_block_barrier();')
-    line('    }')
-  line('  }')
-  line('}')
-  line('')
-  line('GLOBAL WG_SIZE(%d) void %s(soda_hip_args a) {' % (NT, name))
-  for f in shared:
-    line('  __attribute__((shared, aligned(16))) %s lds_%s[2][%d][%d];' % (
-        builtin_type(f.c_type), f.name, ROWS, PITCH))
-  line('  const int tid = __builtin_amdgcn_workitem_id_x();')
-  lo, hi = ['a.box_lo[%d]' % d for d in range(3)], ['a.box_hi[%d]' % d for d in range(3)]
-  if several:
-    # the union of the outputs' boxes is what tiles and chunks cover (the launcher sizes
-    # the grid by the same rule: csrc/schedule.cpp, make_launch)
-    lo, hi = ['lo%d' % d for d in range(3)], ['hi%d' % d for d in range(3)]
-    for d in range(3):
-      for side, shift, sign in (('lo', 8 * d, '-'), ('hi', 24 + 8 * d, '+')):
-        line('  i64 %s%d = 0;' % (side, d))
-        for j in range(n_out):
-          line('  { const i64 e = (a.param[%d] >> %d) & 255; if (e > %s%d) %s%d = e; }'
-               % (1 + j, shift, side, d, side, d))
-        line('  %s%d = a.box_%s[%d] %s %s%d;' % (side, d, side, d, sign, side, d))
-  line('  const i64 x_origin = %s - %s %% %d;' % (lo[0], lo[0], C))
-  line('  const i64 xs = x_origin + (i64)__builtin_amdgcn_workgroup_id_x() * %d;' % TX)
-  line('  const i64 ys = %s + (i64)__builtin_amdgcn_workgroup_id_y() * %d;' % (lo[1], TY))
-  line('  const i64 chunk = a.param[0] > 0 ? a.param[0] : %d;' % chunk_planes)
-  line('  const i64 z0 = %s + (i64)__builtin_amdgcn_workgroup_id_z() * chunk;' % lo[2])
-  # (the same for every work-item of the workgroup: nobody waits at a barrier for them)
-  line('  if (xs >= %s || ys >= %s || z0 >= %s) return;' % tuple(hi))
-  line('  const i64 z1 = z0 + chunk < %s ? z0 + chunk : %s;' % (hi[2], hi[2]))
-  # the box of output j: the launch's box widened by the extras of param[1 + j], each
-  # bound computed where it is used (eighteen 64-bit bounds kept would fill the scalar file)
-  def box_lo(j, d):
-    return '(a.box_lo[%d] - ((a.param[%d] >> %d) & 255))' % (d, 1 + j, 8 * d)
-
-  def box_hi(j, d):
-    return '(a.box_hi[%d] + ((a.param[%d] >> %d) & 255))' % (d, 1 + j, 24 + 8 * d)
-
-  def within(what, first, size):
-    """`what` as a distance from `first`, clamped into [0, size]"""
-    return '(int)(%s - %s < 0 ? 0 : %s - %s > %s ? %s : %s - %s)' % (
-        what, first, what, first, size, size, what, first)
-
-  if several:
-    line('  const int lx = tid %% %d, ly = tid / %d * %d;' % (LX, LX, RW))
-  for j in range(n_out if several else 0):
-    # what output j stores of this tile and chunk, worked out here, once for both paths, and
-    # kept in three VECTOR registers per output (the one-output form leaves a dozen scalar
-    # registers free, fewer than the bounds of three boxes).  Columns and rows: which of
-    # the lane's own cells lie in j's box, bit r * C + c.  Planes: the steps of the plane
-    # loop that compute them (step m computes plane z0 + m - fill)
-    line('  int cells%d = 0;' % j)
-    line('  {')
-    line('    const int sx_lo = %s, sx_hi = %s;' % (within(box_lo(j, 0), 'xs', TX),
-                                                  within(box_hi(j, 0), 'xs', TX)))
-    line('    const int sy_lo = %s, sy_hi = %s;' % (within(box_lo(j, 1), 'ys', TY),
-                                                  within(box_hi(j, 1), 'ys', TY)))
-    for r in range(RW):
-      line('    if (ly + %d >= sy_lo && ly + %d < sy_hi) {%s }' % (r, r, ''.join(
-          ' if (lx * %d + %d >= sx_lo && lx * %d + %d < sx_hi) cells%d |= %d;'
-          % (C, c, C, c, j, 1 << (r * C + c)) for c in range(C))))
-    line('  }')
-    line('  int sn_lo%d = %s + %d, sn_hi%d = %s + %d;' % (
-        j, within(box_lo(j, 2), 'z0', '(z1 - z0)'), fill,
-        j, within(box_hi(j, 2), 'z0', '(z1 - z0)'), fill))
-    line('  %s_opaque(cells%d); %s_opaque(sn_lo%d); %s_opaque(sn_hi%d);'
-         % (name, j, name, j, name, j))
-  line('  const bool interior = xs - %d >= 0 && xs + %d <= a.dims[0] && '
-       'ys - %d >= 0 && ys + %d <= a.dims[1];' % (HXL, TX + HXH, HYL, TY + HYH))
-  args = 'a, %sxs, ys, z0, z1, tid%s' % (
-      ''.join('cells%d, sn_lo%d, sn_hi%d, ' % (j, j, j) for j in range(n_out if several else 0)),
-      ''.join(', lds_%s' % f.name for f in shared))
-  line('  if (interior) %s_tile<true>(%s);' % (name, args))
-  line('  else %s_tile<false>(%s);' % (name, args))
-  line('}')
-  loaded = len(shared) * ROWS * PITCH + (len(fields) - len(shared)) * TX * TY
-  entry = dict(name=name, kind='fused', depth=1, stage=-1, block=[NT, 1, 1],
-               tile=[TX, TY, chunk_planes, 1], origin_align=C, fill_rows=fill, cols=C,
-               rows=RW, w_out=TX, r_out=TY, period=period, est_vgprs=est_vgprs,
-               lds_bytes=geo['lds_bytes'], lds_planes=len(shared), waves=waves,
-               halo=[HXL, HXH, HYL, HYH], loaded_cells=loaded)
-  if several:
-    entry['fields'] = n_out
-  return '\n'.join(o) + '\n', entry
+  print_header(k, o.append)
+  print_tile_prologue(k, o.append)
+  for u in range(k.period):
+    print_step(k, o.append, u, store)
+  o.append('  }\n}\n')
+  print_entry(k, o.append, prologue)
+  return '\n'.join(o) + '\n', table_entry(k)

@@ -1,0 +1,77 @@
+"""The opt-in kernel forms of kernel.generate(): one row per switch, and what follows from it.
+
+A switch is a boolean keyword of generate() that adds one kernel form to the programs in its
+class.  Everything outside the generator that has to know a switch - the command line, the
+generated hosts, the run-time's depth limit, the name of the prebuilt code object - reads it
+here: an opt-in form more is a row more.  Data and pure functions only.
+"""
+import collections
+
+# keyword:     of kernel.generate() and of every function that passes switches on
+# flag, dest:  of the command line (backend.add_arguments), in the order of `--help`
+# suffix:      of the prebuilt code object's name, <app><suffix>.hsaco
+# depth_limit: the form's kernel stores several outputs and is not in the default schedule: it
+#              is launched under soda_hip_plan_set_max_depth(plan, 1)
+# note:        the key of soda_hip_meta under which generate() says what the switch did
+Switch = collections.namedtuple('Switch', 'keyword flag dest help suffix depth_limit note')
+SWITCHES = (
+    Switch('fuse_outputs', '--hip-fuse-outputs', 'hip_fuse_outputs',
+           'one fused depth-1 kernel for a one-pass 2-D / 3-D program '
+           'with several outputs (launched under a depth limit of 1: '
+           'soda_hip_plan_set_max_depth)', '.fused', True, None),
+    Switch('lds_planes', '--hip-lds-planes', 'hip_lds_planes',
+           'one fused depth-1 kernel with the in-plane neighbours in LDS '
+           'for a one-stage 3-D program no other fused form takes (high-order '
+           'stars); it runs in the default schedule', '.lds', False, 'lds_planes'),
+    Switch('lds_fields', '--hip-lds-fields', 'hip_lds_fields',
+           'one fused depth-1 kernel with the in-plane neighbours in LDS '
+           'for a 3-D program with two or three outputs that read inputs only '
+           '(launched under a depth limit of 1: soda_hip_plan_set_max_depth)',
+           '.ldsf', True, 'lds_fields'),
+)
+BY_KEYWORD = {s.keyword: s for s in SWITCHES}
+
+
+def given(on):
+  """The rows of the switches that are on in the keyword arguments `on`, in table order.  A
+  name that is no row is refused as Python refuses an unknown keyword."""
+  for name in on:
+    if name not in BY_KEYWORD:
+      raise TypeError("got an unexpected keyword argument '%s'" % name)
+  return [s for s in SWITCHES if on.get(s.keyword)]
+
+
+def from_args(args):
+  """{keyword: bool} of every switch, read from an argparse namespace."""
+  return {s.keyword: bool(getattr(args, s.dest, False)) for s in SWITCHES}
+
+
+def depth_limit_flags(on):
+  """The flags given among those whose kernel needs the depth limit."""
+  return [s.flag for s in given(on) if s.depth_limit]
+
+
+def depth_limit(on):
+  """Do these switches need the depth limit that admits a kernel over several outputs?"""
+  return bool(depth_limit_flags(on))
+
+
+def keyword_text(on):
+  """`, <keyword>=True` per switch that is on: the tail of a generated call."""
+  return ''.join(', %s=True' % s.keyword for s in given(on))
+
+
+def blob_suffix(on):
+  """What the switches add to a code object's name; `lds_fields` alone decides `.ldsf`."""
+  suffixes = [s.suffix for s in given(on)]
+  return BY_KEYWORD['lds_fields'].suffix if on.get('lds_fields') else ''.join(suffixes)
+
+
+def for_program(spec, **on):
+  """The switches to generate `spec` with when `on` is asked for: a one-pass program with
+  several outputs (kernel_stream2d.rectangular) is in any fused form's class only under
+  `fuse_outputs`, so the LDS form over fields brings it along."""
+  from . import kernel_stream2d
+  if given(on) and on.get('lds_fields') and kernel_stream2d.rectangular(spec):
+    return dict(on, fuse_outputs=True)
+  return on

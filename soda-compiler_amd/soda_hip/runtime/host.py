@@ -17,6 +17,7 @@ import numpy as np
 
 from . import capi
 from ..codegen import spec as specmod
+from ..codegen import switches
 
 
 class DeviceArray:
@@ -484,20 +485,18 @@ class Program:
     return dict(kernel_us=t.kernel_us, launches=t.launches, max_depth=t.max_depth)
 
 
-def open_program(blob=None, source=None, spec=None, fuse_outputs=False, lds_planes=False,
-                 lds_fields=False):
+def open_program(blob=None, source=None, spec=None, **on):
   """`blob`: path to a code object or to kernel text; `source`: kernel text.  With
   neither, the kernels are generated from `spec` and compiled on the spot (hiprtc);
-  `fuse_outputs`, `lds_planes` and `lds_fields` are kernel.generate's switches of those
-  names."""
+  `on`: kernel.generate's switches (codegen/switches.py), by their names."""
+  switches.given(on)
   if blob is not None:
     b = Blob.from_file(blob)
   elif source is not None:
     b = Blob.from_source(source)
   elif spec is not None:
     from ..codegen import kernel
-    b = Blob.from_source(kernel.generate(spec, fuse_outputs=fuse_outputs,
-                                         lds_planes=lds_planes, lds_fields=lds_fields)[0])
+    b = Blob.from_source(kernel.generate(spec, **on)[0])
   else:
     raise ValueError('need a blob path, kernel source or a program spec')
   return Program(b, spec)
@@ -520,8 +519,7 @@ def reference_init(spec, dims):
   return out
 
 
-def app_test(spec, blob, dims, source=None, iterate=None, fuse_outputs=False,
-             lds_planes=False, lds_fields=False):
+def app_test(spec, blob, dims, source=None, iterate=None, **on):
   """The generated `int <app>_test(const char* xclbin, const int dims[4])`
   (reference host.py:984-1167): zero-filled arrays, the reference's input
   pattern, one call of `<app>`, CPU re-computation, comparison on the valid
@@ -530,9 +528,8 @@ def app_test(spec, blob, dims, source=None, iterate=None, fuse_outputs=False,
   from . import selfcheck
   iterate = spec['iterate'] if iterate is None else iterate
   dims = [int(v) for v in list(dims)[:spec['dim']]]
-  prog = open_program(blob=blob, source=source, spec=spec, fuse_outputs=fuse_outputs,
-                      lds_planes=lds_planes, lds_fields=lds_fields)
-  if fuse_outputs or lds_fields:    # a fused kernel over several outputs: under a depth limit
+  prog = open_program(blob=blob, source=source, spec=spec, **on)
+  if switches.depth_limit(on):      # a fused kernel over several outputs: under a depth limit
     prog.set_max_depth(1)
   try:
     inputs = reference_init(spec, dims)

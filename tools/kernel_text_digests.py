@@ -5,10 +5,17 @@ exception.  Needs no GPU and no hipcc.  Two trees that print the same lines gene
 same kernels; run it in both and diff the outputs (a refactoring of the generator's
 selection must give zero differing lines, the error lines included).
 
+The opt-in switches of generate() (fuse_outputs, lds_planes, lds_fields) are cases too, and
+what is derived from them outside the generator has lines of its own: `host/...`, the sha256
+of the generated Python and C++ host texts per combination of switches, and `file/...`, the
+name of the prebuilt code object per combination build() uses.
+
 usage: kernel_text_digests.py [output file]
 """
 import glob
 import hashlib
+import io
+import itertools
 import json
 import os
 import sys
@@ -20,10 +27,16 @@ if '--help' in sys.argv or '-h' in sys.argv:
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'soda-compiler_amd'), os.path.join(ROOT, 'tests')]
 from soda_hip import frontend                                   # noqa: E402
-from soda_hip.codegen import kernel, spec as specmod            # noqa: E402
+from soda_hip.codegen import (host_cpp, host_shim, kernel, kernel_fields2d,  # noqa: E402
+                              kernel_fields3d, kernel_stream3d_lds)
+from soda_hip.codegen import spec as specmod                    # noqa: E402
+import __graft_entry__ as entry                                 # noqa: E402
 # the option sets of the GPU tests come from the tests themselves (importing them needs no GPU)
 import test_gpu_memory_contract as contract                     # noqa: E402
 import test_gpu_parity as parity                                # noqa: E402
+import test_lds3d_codegen as lds3d                              # noqa: E402
+import test_lds3d_fields_codegen as lds3d_fields                # noqa: E402
+import test_rect_codegen as rect                                # noqa: E402
 
 SAMPLES = os.path.join(ROOT, 'tests', 'samples')
 ITERATES = (None, 1, 3, 4, 8, 15, 100, 1000)
@@ -81,6 +94,60 @@ for _, _, o in LITERAL:
   if o and o not in CROSSED:
     CROSSED.append(o)
 
+SWITCHES = ('fuse_outputs', 'lds_planes', 'lds_fields')
+# the samples the LDS-plane forms take, with the switches that give them their kernel
+LDS_SAMPLES = [(app, dict(lds_planes=True)) for app in lds3d.APPS] + [
+    (app, lds3d_fields.switches(app)) for app in lds3d_fields.APPS]
+HOST_PROGRAMS = ('jacobi2d', 'grad2d', 'grad3d', 'star3d', 'acoustic3d', 'deriv3d')
+HOST_CPP_SWITCHES = ('fuse_outputs', 'lds_fields')      # the keywords host_cpp.print_code took
+
+
+def combinations(names):
+  """Every subset of the switches `names`, as keyword arguments (those that are on)."""
+  return [{n: True for n, on in zip(names, bits) if on}
+          for bits in itertools.product((False, True), repeat=len(names))]
+
+
+def inline_texts():
+  """(key, program text): what tests/test_rect_codegen.py, test_lds3d_codegen.py and
+  test_lds3d_fields_codegen.py feed to generate() besides the samples.  The module-level
+  texts are imported; those the rect tests build inside their functions are restated from
+  the tests' own header line and limits."""
+  for name in ('TWO_PLANES', 'TWO_STAGES', 'TWO_OUTPUTS', 'TWO_BYTES'):
+    yield 'lds3d/' + name, getattr(lds3d, name)
+  yield 'lds3d/axis', lds3d._HEAD % 'axis' + 'input float: a(32, 32, *)\n' \
+      'output float: b(0, 0, 0) = a(0, 0, 3) + a(0, 0, -3)\n'
+  for name in ('STAGE_READS_STAGE', 'FOUR_OUTPUTS', 'MIXED_WIDTHS', 'TWO_BYTES', 'TWO_PLANES'):
+    yield 'lds3d_fields/' + name, getattr(lds3d_fields, name)
+  head = rect._HEAD
+  for dim, limit, tile in ((2, kernel_fields2d.MAX_OUTPUTS, '(32, *)'),
+                           (3, kernel_fields3d.MAX_OUTPUTS, '(32, 32, *)')):
+    zero = ', '.join('0' * dim)
+    one = zero.replace('0', '1', 1)
+    for n in (limit, limit + 1):
+      yield 'rect/many/%d/%d' % (dim, n), head % ('many', 1) + 'input float: a%s\n' % tile + \
+          ''.join('output float: o%d(%s) = a(%s) * %d.0f\n' % (j, zero, zero, j + 2)
+                  for j in range(n))
+    yield 'rect/wide_out/%d' % dim, head % ('widths', 1) + 'input float: a%s\n' % tile + \
+        'output float: o(%s) = a(%s) * 2.0f\noutput double: p(%s) = a(%s) * 0.5\n' % (
+            (zero,) * 4)
+    yield 'rect/wide_local/%d' % dim, head % ('widths', 1) + 'input float: a%s\n' % tile + \
+        'local double: m(%s) = a(%s) * 0.5\n' % (zero, zero) + \
+        'output float: o(%s) = float(m(%s)) + a(%s)\n' % (zero, one, zero) + \
+        'output float: p(%s) = float(m(%s)) - a(%s)\n' % (zero, zero, one)
+    for n in (4, 5, 7):
+      rows = ['input float: f%d%s' % (j, tile if j == n - 1 else '') for j in range(n)]
+      rows += ['output float: o(%s) = %s' % (zero, ' + '.join('f%d(%s)' % (j, zero)
+                                                               for j in range(n))),
+               'output float: p(%s) = f0(%s) * 2.0f' % (zero, one)]
+      yield 'rect/wide/%d/%d' % (dim, n), head % ('wide', 1) + '\n'.join(rows) + '\n'
+  far2 = head % ('far', 1) + 'input float: a(32, *)\n' \
+      'output float: o(0, 0) = a(0, 0) + a(5, 0)\noutput float: p(0, 0) = a(0, 1)\n'
+  yield 'rect/far2', far2
+  yield 'rect/near2', far2.replace('a(5, 0)', 'a(4, 0)')
+  yield 'rect/far3', head % ('far', 1) + 'input float: a(32, 32, *)\n' \
+      'output float: o(0, 0, 0) = a(0, 0, 0) + a(-3, 0, 0)\noutput float: p(0, 0, 0) = a(0, 1, 0)\n'
+
 
 def spec_of(app, iterate):
   if app in contract.TEXT:
@@ -124,9 +191,65 @@ def cases():
     for app in FAMILIES:
       yield 'crossed/%d/%s/%s' % (n, app, show(options)), \
           (lambda a=app: spec_of(a, None if a == 'denoise3d' else 31)), options
+  # the opt-in switches: each alone and all together on every sample ...
+  together = [{n: True} for n in SWITCHES] + [{n: True for n in SWITCHES}]
+  for path in sorted(glob.glob(os.path.join(SAMPLES, '*.soda')) +
+                     glob.glob(os.path.join(SAMPLES, 'extra', '*.soda'))):
+    app = os.path.basename(path)[:-5]
+    for on in together:
+      yield 'switch/%s/%s' % (app, show(on)), (lambda a=app: spec_of(a, None)), on
+  # ... the samples the LDS-plane forms take in every shape (refused ones included) and at
+  # the iteration counts that change their default depths ...
+  for app, on in LDS_SAMPLES:
+    for shape in kernel_stream3d_lds.SHAPES:
+      yield 'lds_shape/%s/%s' % (app, show(shape)), (lambda a=app: spec_of(a, None)), \
+          dict(on, lds_shape=shape)
+    for iterate in (1, 2, 3, None):
+      yield 'lds_iterate/%s/%s' % (app, iterate), (lambda a=app, i=iterate: spec_of(a, i)), on
+  # ... and the program texts of the switches' own tests
+  for key, text in inline_texts():
+    make = lambda t=text: specmod.spec_from_stencil(frontend.loads(t))
+    for on in [{}] + together:
+      yield 'inline/%s/%s' % (key, show(on)), make, on
+
+
+def digest(text):
+  return hashlib.sha256(text.encode()).hexdigest()
+
+
+def host_lines():
+  """`host/...`: the generated host texts per combination of switches, one program per
+  class; `file/...`: the code object names of the combinations build() uses."""
+  show = lambda o: ','.join(sorted(o)) or '-'
+  for app in HOST_PROGRAMS:
+    spec = spec_of(app, None)
+    for on in combinations(SWITCHES):
+      out = io.StringIO()
+      try:
+        host_shim.print_code(spec, out, **on)
+        yield 'host/shim/%s/%s %s' % (app, show(on), digest(out.getvalue()))
+      except Exception as e:
+        yield 'host/shim/%s/%s %s: %s' % (app, show(on), type(e).__name__, e)
+    for on in combinations(HOST_CPP_SWITCHES):
+      out = io.StringIO()
+      try:
+        table = kernel.generate(spec, **on)[1]
+        host_cpp.print_code(spec, table, out, lowered=specmod.inline_pointwise(spec), **on)
+        yield 'host/cpp/%s/%s %s' % (app, show(on), digest(out.getvalue()))
+      except Exception as e:
+        yield 'host/cpp/%s/%s %s: %s' % (app, show(on), type(e).__name__, e)
+  every = entry.APPS + entry.EXTRA_APPS + entry.FIELD_APPS + entry.FIELD3D_APPS + \
+      entry.FIELD1D_APPS + entry.RECT_APPS + entry.LDS3D_APPS + entry.LDS_FIELDS_APPS
+  for apps, on in ((every, {}), (entry.FUSED_OUTPUT_APPS, dict(fuse_outputs=True)),
+                   (entry.LDS3D_APPS, dict(lds_planes=True)),
+                   (entry.LDS_FIELDS_APPS, dict(lds_fields=True))):
+    for app in apps:
+      yield 'file/%s/%s %s' % (app, show(on), os.path.basename(entry.blob_path(app, **on)))
 
 
 if __name__ == '__main__':
   out = open(sys.argv[1], 'w') if len(sys.argv) > 1 else sys.stdout
   for case in cases():
     out.write(line(*case) + '\n')
+  for text in host_lines():
+    out.write(text + '\n')

@@ -137,10 +137,9 @@ def main():
     spec = specmod.spec_from_stencil(frontend.load(entry.sample_path(app)))
     iterate = spec['iterate']
     if args.fields:
-      from soda_hip.codegen import kernel_stream2d
+      from soda_hip.codegen import switches
       blob = entry.blob_path(app, lds_fields=True)
-      table = kernel.generate(spec, lds_fields=True,
-                              fuse_outputs=kernel_stream2d.rectangular(spec))[1]
+      table = kernel.generate(spec, **switches.for_program(spec, lds_fields=True))[1]
     else:
       blob = entry.blob_path(app, lds_planes=True)
       table = kernel.generate(spec, lds_planes=True)[1]
