@@ -26,6 +26,10 @@ The unit holds
       3-D, two or three outputs that read inputs only, windows wider than a lane's columns:
                         the same form over several outputs (<app>_fused_k1lf), only with
                         `lds_fields=True` and only where no other form made a depth-1 kernel;
+      3-D, either of the two with an input read in-plane in SEVERAL planes (mixed z terms):
+                        the same form with a ring of planes in LDS (<app>_fused_k1r, _k1rf),
+                        only with `lds_ring=True` and only where no other form made a
+                        depth-1 kernel;
   * `soda_hip_meta`, JSON describing the program and the kernel table, which
     libsoda_hip.so reads back from the loaded blob.
 
@@ -849,27 +853,34 @@ def deep3d_kernels(req, notes):
       yield found
 
 
-# The two LDS-plane forms (kernel_stream3d_lds), one per switch.  `fields`: the form over
-# several outputs.  `refusals`: in the order they are checked, (condition, note) over the
-# request and the name of a fused depth-1 kernel another family made ('' if none).  A
-# rectangular program is in the fields form's class, as in anyone's, only under
-# `fuse_outputs` (Request.rect).
-LdsForm = collections.namedtuple('LdsForm', 'switch fields refusals')
+# The LDS-plane forms (kernel_stream3d_lds), one per switch.  `fields`: the form over
+# several outputs - for the plane ring, which takes one output or several, a function of the
+# request.  `ring`: several planes of an input in LDS.  `refusals`: in the order they are
+# checked, (condition, note) over the request and the name of a fused depth-1 kernel another
+# family made ('' if none).  A rectangular program is in the fields form's class, as in
+# anyone's, only under `fuse_outputs` (Request.rect).
+LdsForm = collections.namedtuple('LdsForm', 'switch fields ring refusals')
 _NOT_3D = (lambda req, have: req.spec['dim'] != 3,
            'not fused: the LDS-plane form handles 3-D programs')
 _NOT_WANTED = (lambda req, have: bool(have), 'not wanted: {have}')
-LDS_PLANES = LdsForm('lds_planes', False, (_NOT_3D, _NOT_WANTED))
-LDS_FIELDS = LdsForm('lds_fields', True, (
+_NOT_RECT = (lambda req, have: kernel_stream2d.rectangular(req.spec) and not req.rect,
+             'not fused: a one-pass program with several outputs is fused only with fuse_outputs')
+LDS_PLANES = LdsForm('lds_planes', False, False, (_NOT_3D, _NOT_WANTED))
+LDS_FIELDS = LdsForm('lds_fields', True, False, (
     (lambda req, have: len(req.spec['outputs']) < 2, 'not concerned: one output'),
-    _NOT_WANTED, _NOT_3D,
-    (lambda req, have: kernel_stream2d.rectangular(req.spec) and not req.rect,
-     'not fused: a one-pass program with several outputs is fused only with fuse_outputs')))
+    _NOT_WANTED, _NOT_3D, _NOT_RECT))
+LDS_RING = LdsForm('lds_ring', lambda req: len(req.spec['outputs']) > 1, True, (
+    _NOT_3D, _NOT_WANTED,
+    (lambda req, have: all(len(planes) <= 1 for planes in
+                           kernel_stream3d_lds.planes_off_axis(req.spec).values()),
+     'not concerned: one plane per input, lds_planes / lds_fields take it'),
+    _NOT_RECT))
 
 
 def lds3d_kernels(form, req, notes):
   """3-D programs no other family gave a fused depth-1 kernel, when generate() was asked
-  for this LDS-plane form: kernel_stream3d_lds, in the first shape that fits.  The two forms
-  come last in FAMILIES.  What a form did goes into req.meta_notes under its switch's key of
+  for this LDS-plane form: kernel_stream3d_lds, in the first shape that fits.  The forms
+  come last in FAMILIES, the plane ring last of them.  What a form did goes into req.meta_notes under its switch's key of
   soda_hip_meta, not into `notes`: apart from the metadata, the text of a program the form
   does not take is the same with and without the switch."""
   if not req.on[form.switch]:
@@ -881,8 +892,11 @@ def lds3d_kernels(form, req, notes):
       req.meta_notes[key] = note.format(have=have)
       return
   shape = form_options('stream3d_lds', req.options).get('lds_shape')
-  found, error = first_fusable(req.spec, 1, [(kernel_stream3d_lds.emit, dict(
-      dict(zip(('waves', 'rows', 'lanes_x'), shape)) if shape else {}, fields=form.fields))])
+  kwargs = dict(zip(('waves', 'rows', 'lanes_x'), shape)) if shape else {}
+  kwargs['fields'] = form.fields(req) if callable(form.fields) else form.fields
+  if form.ring:
+    kwargs['ring'] = True
+  found, error = first_fusable(req.spec, 1, [(kernel_stream3d_lds.emit, kwargs)])
   if found is None:
     req.meta_notes[key] = 'not fused: %s' % error
     return
@@ -895,12 +909,14 @@ def lds3d_kernels(form, req, notes):
 FAMILIES = (fields2d_kernels, fields3d_kernels, fields1d_kernels, stream1d_kernels,
             stream2d_kernels, stream3d_kernels, deep3d_kernels,
             functools.partial(lds3d_kernels, LDS_PLANES),
-            functools.partial(lds3d_kernels, LDS_FIELDS))
+            functools.partial(lds3d_kernels, LDS_FIELDS),
+            functools.partial(lds3d_kernels, LDS_RING))
 
 
 def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
              fused=True, depths=None, inline=True, wave_groups=None,
-             fuse_outputs=False, lds_planes=False, lds_fields=False, **fused_options):
+             fuse_outputs=False, lds_planes=False, lds_fields=False, lds_ring=False,
+             **fused_options):
   """Returns (kernel text, kernel table).  `depths` overrides the default set
   of fused depths (depth 1 is always included: the scheduler needs it).
   `fuse_outputs`: a one-pass 2-D / 3-D program with several outputs that is not
@@ -919,7 +935,15 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   gives a fused depth-1 kernel; launched under a depth limit of 1 like every fused kernel
   over several outputs.  Every other program keeps its table and, apart from the entry
   `lds_fields` of soda_hip_meta, its text.  The two LDS switches concern disjoint programs
-  and may be given together."""
+  and may be given together.
+  `lds_ring`: the same form with a RING of planes in LDS, `<app>_fused_k1r` for one output
+  and `<app>_fused_k1rf` for two or three, for a 3-D program in the scope of the two forms
+  above that reads an input off the z axis in more than one plane (mixed derivatives
+  d2/dxdz, rotated operators) and that no other form gives a fused depth-1 kernel; launched
+  under a depth limit of 1.  A program that reads every input off the z axis in at most one
+  plane is not concerned, so the three LDS switches concern disjoint programs and may be
+  given together.  Every other program keeps its table and, apart from the entry `lds_ring`
+  of soda_hip_meta, its text."""
   # kernels are generated from the LOWERED program (pointwise-only locals folded
   # into their readers); the blob is still identified by the source program
   source = spec
@@ -936,7 +960,7 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   notes = []
   req = Request(spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
                 fused_options, dict(fuse_outputs=fuse_outputs, lds_planes=lds_planes,
-                                    lds_fields=lds_fields))
+                                    lds_fields=lds_fields, lds_ring=lds_ring))
   for family in FAMILIES if fused else ():
     for ftext, entry in family(req, notes):
       parts.append(ftext)

@@ -22,7 +22,8 @@ High-order stars (the 8th-order Laplacian, iso3dfd) therefore get this shape ins
     registers, one plane ahead: no LDS, no window.
 
 Scope: one stage that is the one output, any number of inputs, one element width of 4 or 8
-bytes, and per input ONE plane offset at which it is read off the z axis.  Depth 1 only.
+bytes, and per input ONE plane offset at which it is read off the z axis (several with
+`ring=True`, below).  Depth 1 only.
 Array edges as in kernel_stream3d: loads clamped into the array on all six sides, stores
 inside the box only, any array size.
 
@@ -34,6 +35,19 @@ a box of its own under kernel_fields3d's contract: the launch's box is the inter
 param[1 + j] carries output j's six extras, tiles and z chunks cover the union, and output
 j stores a cell only inside j's box on all three axes.  An output that is one load at
 (0, 0, 0) of an input of its own type is stored straight from the window registers.
+
+`ring=True` lifts the one-plane condition of both forms, `<app>_fused_k1r` and `_k1rf`
+(mixed derivatives d2/dxdz, lopsided windows, coupled fields).  An input read off the z axis
+in the planes `planes`, plo = min, phi = max, gets a RING of S = phi - plo + 2 LDS slots:
+at the step of output plane z they hold the planes z + plo .. z + phi, gaps nobody reads
+included, and the step fills the slot of plane z + phi + 1 - own cells from the window
+registers, the halo ring from the registers fetched at this step.  That slot held plane
+z + plo - 1 (or an earlier one), last read one step and one barrier ago: one barrier per
+plane still suffices.  The unroll period is a common multiple of every register slot count
+and every S, either padded up to a divisor (ring_rotation), so every slot index stays a
+literal; the two-slot form above is the case S = 2.  The halos hx / hy are hulls over all
+planes; the lane's own cells are never read from LDS, in any plane.  The ring may take the
+CU's whole LDS (RING_LDS_CAP); the two single-plane forms keep LDS_CAP.
 """
 import types
 
@@ -43,37 +57,43 @@ from .kernel_fields3d import MAX_OUTPUTS
 from .kernel_stream2d import LANES, NotFusable, multi_field, rectangular
 
 LDS_CAP = 65536
+RING_LDS_CAP = 163840          # of the plane-ring form: the LDS of a gfx950 CU
 # (wavefronts, rows per lane, lanes per tile row) that emit() chooses from when the caller
 # names none: shapes_by_loaded_cells
 SHAPES = tuple((w, rw, lx) for w in (8, 4) for rw in (4, 2, 1) for lx in (64, 32, 16))
 
 
-def kernel_name(spec, fields=False):
-  return '%s_fused_k1l%s' % (spec['app_name'], 'f' if fields else '')
+def kernel_name(spec, fields=False, ring=False):
+  return '%s_fused_k1%s%s' % (spec['app_name'], 'r' if ring else 'l', 'f' if fields else '')
 
 
 class Field:
-  """How the stage reads one input: its z window, and what it reads in the plane `zc`."""
+  """How the stage reads one input: its z window, and what it reads in the plane `zc` - with
+  `ring` in the planes `planes`, of which [plo, phi] is the hull: the planes that lie in LDS."""
 
-  def __init__(self, name, c_type, rels):
+  def __init__(self, name, c_type, rels, ring=False):
     self.name, self.c_type, self.rels = name, c_type, rels
     off = [r for r in rels if (r[0], r[1]) != (0, 0)]
     planes = sorted({r[2] for r in off})
-    if len(planes) > 1:
+    if len(planes) > 1 and not ring:
       raise NotFusable('input %s is read off the z axis at plane offsets %s: one plane of an '
                        'input lies in LDS' % (name, ' and '.join(map(str, planes))))
     self.lds = bool(off)
     self.zc = planes[0] if off else None
+    self.planes = planes
+    self.plo, self.phi = (planes[0], planes[-1]) if off else (None, None)
+    # LDS slots: the planes z + plo .. z + phi a step reads and the one it fills
+    self.lds_slots = self.phi - self.plo + 2 if off else 0
     self.zlo, self.zhi = min(r[2] for r in rels), max(r[2] for r in rels)
     self.keep = self.zhi - self.zlo + 2          # the window and the plane loaded ahead
     self.hx = (max([0] + [-r[0] for r in off]), max([0] + [r[0] for r in off]))
     self.hy = (max([0] + [-r[1] for r in off]), max([0] + [r[1] for r in off]))
 
 
-def analyse(spec, fields=False):
+def analyse(spec, fields=False, ring=False):
   """(stages, [Field]) of a program in scope; NotFusable names what keeps it out.  `fields`:
   the scope of the form over several outputs, where a Field is the union of every stage's
-  reads of that input."""
+  reads of that input.  `ring`: an input may be read off the z axis in several planes."""
   if spec['dim'] != 3:
     raise NotFusable('the LDS-plane form handles 3-D programs')
   if fields:
@@ -113,7 +133,7 @@ def analyse(spec, fields=False):
       rels += [tuple(rel) for name, rel in stage['loads']
                if name == t['name'] and tuple(rel) not in rels]
     if rels:
-      found.append(Field(t['name'], t['c_type'], rels))
+      found.append(Field(t['name'], t['c_type'], rels, ring))
   if not any(f.lds for f in found):
     raise NotFusable('no read off the z axis: nothing for an LDS plane to share')
   return spec['stages'], found
@@ -136,8 +156,20 @@ def passed_through(spec, stage):
   return name if types.get(name) == stage['c_type'] else None
 
 
-def geometry(fields, elem, waves, rows, lanes_x):
-  """Tile, LDS slot and halo of one shape, all in cells."""
+def planes_off_axis(spec):
+  """{input: the sorted z offsets at which the program reads it at (dx, dy) != (0, 0)} of a
+  3-D program."""
+  planes = {t['name']: set() for t in spec['inputs']}
+  for stage in spec['stages']:
+    for name, rel in stage['loads']:
+      if name in planes and (rel[0], rel[1]) != (0, 0):
+        planes[name].add(rel[2])
+  return {name: sorted(p) for name, p in planes.items()}
+
+
+def geometry(fields, elem, waves, rows, lanes_x, lds_slots=None):
+  """Tile, LDS slot and halo of one shape, all in cells.  `lds_slots`: {input: slots} of the
+  plane ring; two slots per input without it."""
   C = 16 // elem
   shared = [f for f in fields if f.lds]
   hx = [max(f.hx[s] for f in shared) for s in (0, 1)]
@@ -148,13 +180,15 @@ def geometry(fields, elem, waves, rows, lanes_x):
   return dict(C=C, TX=tx, TY=ty, HXL=hxl, HXH=hxh, HYL=hy[0], HYH=hy[1], PITCH=pitch,
               ROWS=slot_rows, threads=waves * LANES,
               halo_vectors=(slot_rows * pitch - tx * ty) // C,
-              lds_bytes=len(shared) * 2 * slot_rows * pitch * elem,
+              lds_bytes=sum(lds_slots[f.name] if lds_slots else 2 for f in shared) *
+              slot_rows * pitch * elem,
               loaded=slot_rows * pitch / float(tx * ty))
 
 
-def lds_vectors(fields, C, rows):
+def lds_vectors(fields, C, rows, ring=False):
   """The (field, row, vector) triples a lane reads from LDS per step: every in-plane read of
-  every one of its cells, less what lies in its own cells."""
+  every one of its cells, less what lies in its own cells.  `ring`: (field, plane, row,
+  vector), a vector of every plane apart."""
   seen = []
   for f in fields:
     for dx, dy, dz in f.rels:
@@ -162,27 +196,35 @@ def lds_vectors(fields, C, rows):
         continue
       for r in range(rows):
         for c in range(C):
-          key = (f.name, r + dy, (c + dx) // C)
-          if not (key[2] == 0 and 0 <= key[1] < rows) and key not in seen:
+          row, vi = r + dy, (c + dx) // C
+          key = (f.name, dz, row, vi) if ring else (f.name, row, vi)
+          if not (vi == 0 and 0 <= row < rows) and key not in seen:
             seen.append(key)
   return seen
 
 
-def estimate_vgprs(fields, elem, geo, rows, computed=1):
+def estimate_vgprs(fields, elem, geo, rows, computed=1, ring=False):
   """`computed`: the outputs whose cells are computed (all but those passed through)."""
   per, C = max(1, elem // 4), geo['C']
   shared = [f for f in fields if f.lds]
   halo_loads = -(-geo['halo_vectors'] // geo['threads'])
-  return (sum(f.keep for f in fields) * rows * C * per +     # windows, planes ahead
-          len(lds_vectors(fields, C, rows)) * 4 +            # neighbours out of LDS
+  # the plane-ring form also counts the sums in flight: the compiler interleaves the chains
+  # of a lane's RW x C cells, some four partial terms per cell register.  Without them the
+  # estimate was 21 to 68 registers short of hipcc's count at two and four rows per lane
+  # (cross3d 233 for 268, skewcross3d 242 for 302) and the first shape by loaded cells
+  # spilled; with them it is at most 9 below and 15 above it for the three samples in every
+  # shape that fits
+  in_flight = 4 * rows * C * per if ring else 0
+  return (sum(f.keep for f in fields) * rows * C * per + in_flight +  # windows, planes ahead
+          len(lds_vectors(fields, C, rows, ring)) * 4 +      # neighbours out of LDS
           computed * rows * C * per +                        # the output cells
           halo_loads * (4 * len(shared) + 5) + 24)           # halo ring and its addresses
 
 
-def shapes_by_loaded_cells(spec, shapes=SHAPES, fields=False):
+def shapes_by_loaded_cells(spec, shapes=SHAPES, fields=False, ring=False):
   """The shapes ordered by cells loaded over cells stored, (TX + hx)(TY + hy) / (TX TY),
   least first (among equals as listed: more wavefronts, taller lanes first)."""
-  _, fields = analyse(spec, fields)
+  _, fields = analyse(spec, fields, ring)
   elem = specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
   return sorted(shapes, key=lambda s: geometry(fields, elem, *s)['loaded'])
 
@@ -204,29 +246,61 @@ def rotation(fields, max_period):
   return best[1], best[2]
 
 
-def fit(fields, elem, computed, shape, max_period, vgpr_budget):
+def ring_rotation(fields, max_period, lds_slots_cap):
+  """(period, {field: register slots}, {shared field: LDS slots}) of the plane-ring form: the
+  period is a common multiple of all of them, so that the register slot and the LDS slot of
+  every access are known when the text is printed.  A count is padded up to a divisor of the
+  period, LDS slots no further than `lds_slots_cap` in all; registers are the scarcer, so
+  the fewest register slots win, then the fewest LDS slots, then the shortest period."""
+  shared = [f for f in fields if f.lds]
+  best = None
+  for period in range(2, max_period + 1):
+    if max(max(f.keep, f.lds_slots) for f in fields) > period:
+      continue
+    divisors = [d for d in range(1, period + 1) if period % d == 0]
+    slots = {f.name: min(d for d in divisors if d >= f.keep) for f in fields}
+    lds_slots = {f.name: min(d for d in divisors if d >= f.lds_slots) for f in shared}
+    if sum(lds_slots.values()) > lds_slots_cap:
+      continue
+    cost = (sum(slots.values()), sum(lds_slots.values()), period)
+    if best is None or cost < best[0]:
+      best = (cost, period, slots, lds_slots)
+  if best is None:
+    raise NotFusable('z window deeper than the rotation period limit %d' % max_period)
+  return best[1:]
+
+
+def fit(fields, elem, computed, shape, max_period, vgpr_budget, ring=False):
   """The figures of one shape - its geometry, estimated VGPRs and rotation - as the record
   the printers share; NotFusable where it exceeds the LDS cap, the register budget or the
   rotation period limit."""
-  k = types.SimpleNamespace(waves=shape[0], RW=shape[1], LX=shape[2],
-                            **geometry(fields, elem, *shape))
+  k = types.SimpleNamespace(waves=shape[0], RW=shape[1], LX=shape[2], ring=ring)
+  shared = [f for f in fields if f.lds]
+  k.lds_slots = {f.name: f.lds_slots if ring else 2 for f in shared}
+  vars(k).update(geometry(fields, elem, *shape, lds_slots=k.lds_slots))
   k.shape_text = '%d x %d tiles (%d wavefronts, %d rows per lane)' % (k.TX, k.TY, k.waves, k.RW)
-  if k.lds_bytes > LDS_CAP:
+  cap = RING_LDS_CAP if ring else LDS_CAP
+  if k.lds_bytes > cap:
     raise NotFusable('%s would need %d bytes of LDS (cap %d)' % (k.shape_text, k.lds_bytes,
-                                                                  LDS_CAP))
-  k.est_vgprs = estimate_vgprs(fields, elem, vars(k), k.RW, computed=computed)
+                                                                  cap))
+  k.est_vgprs = estimate_vgprs(fields, elem, vars(k), k.RW, computed=computed, ring=ring)
   if k.est_vgprs > vgpr_budget:
     raise NotFusable('%s would need about %d VGPRs (budget %d)' % (k.shape_text, k.est_vgprs,
                                                                     vgpr_budget))
-  k.period, k.slots = rotation(fields, max_period)
+  if ring:
+    slot_bytes = k.ROWS * k.PITCH * elem
+    k.period, k.slots, k.lds_slots = ring_rotation(fields, max_period, cap // slot_bytes)
+    k.lds_bytes = sum(k.lds_slots.values()) * slot_bytes
+  else:
+    k.period, k.slots = rotation(fields, max_period)
   return k
 
 
-def first_fit(spec, several, fits):
+def first_fit(spec, several, fits, ring=False):
   """fits(shape) of the first of shapes_by_loaded_cells that it does not refuse; when all are
   refused, the FIRST shape's error."""
   error = None
-  for shape in shapes_by_loaded_cells(spec, fields=several):
+  for shape in shapes_by_loaded_cells(spec, fields=several, ring=ring):
     try:
       return fits(shape)
     except NotFusable as e:
@@ -250,9 +324,20 @@ def halo_guard(k, i):
   return 'if (tid + %d < %d) ' % (i * k.threads, k.halo_vectors)
 
 
-def lds_vector(field, row, vi):
-  """The vector `vi` of row `row`, relative to the lane's own, read from `field`'s plane."""
-  return 'l_%s_%s_%s' % (field, str(row).replace('-', 'm'), str(vi).replace('-', 'm'))
+def lds_vector(field, row, vi, dz=None):
+  """The vector `vi` of row `row`, relative to the lane's own, read from `field`'s plane -
+  in the plane-ring form from its plane z + `dz`."""
+  name = lambda v: str(v).replace('-', 'm')
+  if dz is None:
+    return 'l_%s_%s_%s' % (field, name(row), name(vi))
+  return 'l_%s_p%s_%s_%s' % (field, name(dz), name(row), name(vi))
+
+
+def lds_slot(k, f, u, dz):
+  """The LDS slot in which plane z + dz of `f` lies at unrolled step u, phi + 1 being the
+  plane the step fills.  Two slots, one plane: u % 2 is read, (u + 1) % 2 is filled."""
+  assert f.plo <= dz <= f.phi + 1
+  return (u + dz - f.plo) % k.lds_slots[f.name]
 
 
 def own(k, f, u, dz, r, c):
@@ -273,20 +358,25 @@ def load_of(k, u, r, c):
     ry, vi, e = r + dy, (c + dx) // k.C, (c + dx) % k.C
     if vi == 0 and 0 <= ry < k.RW:
       return own(k, f, u, dz, ry, e)
-    return '%s[%d]' % (lds_vector(tensor, ry, vi), e)
+    return '%s[%d]' % (lds_vector(tensor, ry, vi, dz if k.ring else None), e)
   return load
 
 
 def print_header(k, line):
   """The comment that describes the kernel, and the vector types of its tensors."""
-  line('// fused depth-1 3-D kernel%s, LDS planes: %s, halo x %d+%d y %d+%d,'
-       % (k.over, k.shape_text, k.HXL, k.HXH, k.HYL, k.HYH))
+  line('// fused depth-1 3-D kernel%s, LDS %s: %s, halo x %d+%d y %d+%d,'
+       % (k.over, 'plane ring' if k.ring else 'planes', k.shape_text, k.HXL, k.HXH, k.HYL,
+          k.HYH))
   line('// %d bytes of LDS, rotation period %d, %d planes walked before the first stored one, '
        '~%d VGPRs' % (k.lds_bytes, k.period, k.fill, k.est_vgprs))
   for f in k.fields:
+    in_lds = ''
+    if f.lds and k.ring:
+      in_lds = ', planes %+d to %+d in %d LDS slots' % (f.plo, f.phi, k.lds_slots[f.name])
+    elif f.lds:
+      in_lds = ', plane %+d in LDS' % f.zc
     line('//   %-12s z window [%d, %d] in %d register slots%s' % (
-        f.name, f.zlo, f.zhi, k.slots[f.name],
-        ', plane %+d in LDS' % f.zc if f.lds else ''))
+        f.name, f.zlo, f.zhi, k.slots[f.name], in_lds))
   for c_type in sorted({f.c_type for f in k.fields} | {st['c_type'] for st in k.stages}):
     k.vec[c_type] = 'vec_%s_%s' % (k.name, c_type)
     k.lvec[c_type] = 'lvec_%s_%s' % (k.name, c_type)
@@ -389,8 +479,8 @@ def print_halo_fetch(k, line):
   for f in k.shared:
     T, V = builtin_type(f.c_type), k.vec[f.c_type]
     line('      %s halo_%s[%d];' % (k.lvec[f.c_type], f.name, k.K))
-    line('      {  // halo ring of plane z%+d of %s' % (f.zc + 1, f.name))
-    line('        %s' % clamped_plane('z + %d' % (f.zc + 1)))
+    line('      {  // halo ring of plane z%+d of %s' % (f.phi + 1, f.name))
+    line('        %s' % clamped_plane('z + %d' % (f.phi + 1)))
     line('        const %s* p = g_%s + zz * plane;' % (T, f.name))
     for i in range(k.K):
       line('        halo_%s[%d] = 0;' % (f.name, i))
@@ -406,11 +496,16 @@ def print_halo_fetch(k, line):
 
 
 def print_lds_reads(k, line, u):
-  """The in-plane neighbours of the lane's cells, as whole vectors from the slot u % 2."""
-  for fname, ry, vi in lds_vectors(k.fields, k.C, k.RW):
-    V = k.lvec[k.by_name[fname].c_type]
+  """The in-plane neighbours of the lane's cells, as whole vectors from the slot u % 2 - in
+  the plane-ring form from the slot of each vector's plane."""
+  for key in lds_vectors(k.fields, k.C, k.RW, k.ring):
+    fname, ry, vi = key[0], key[-2], key[-1]
+    f = k.by_name[fname]
+    dz = key[1] if k.ring else f.zc
+    V = k.lvec[f.c_type]
     line('        const %s %s = *(const %s*)&lds_%s[%d][%d + ly + %d][%d + lx * %d + %d];'
-         % (V, lds_vector(fname, ry, vi), V, fname, u % 2, k.HYL, ry, k.HXL, k.C, vi * k.C))
+         % (V, lds_vector(fname, ry, vi, dz if k.ring else None), V, fname,
+            lds_slot(k, f, u, dz), k.HYL, ry, k.HXL, k.C, vi * k.C))
 
 
 def print_compute(k, line, stage, u, indent):
@@ -474,19 +569,31 @@ def print_lds_fill(k, line, u):
   """The other slot gets the next step's plane: own cells from the window, halo ring."""
   for f in k.shared:
     V = k.lvec[f.c_type]
+    slot = lds_slot(k, f, u, f.phi + 1)
+    if k.ring:
+      # the slot held plane z + plo - 1 or, in a padded ring, an earlier one: nobody has read
+      # it since the step before this one, and that step's barrier lies between - one barrier
+      # per plane still suffices
+      line('      // plane z%+d of %s into the slot of plane z%+d: last read %d step(s) ago, a '
+           'barrier lies between' % (f.phi + 1, f.name, f.phi + 1 - k.lds_slots[f.name],
+                                     k.lds_slots[f.name] - (f.phi - f.plo + 1)))
     for r in range(k.RW):
       line('      { %s v;%s *(%s*)&lds_%s[%d][%d + ly + %d][%d + lx * %d] = v; }' % (
-          V, ''.join(' v[%d] = %s;' % (c, own(k, f, u, f.zc + 1, r, c)) for c in range(k.C)),
-          V, f.name, (u + 1) % 2, k.HYL, r, k.HXL, k.C))
+          V, ''.join(' v[%d] = %s;' % (c, own(k, f, u, f.phi + 1, r, c)) for c in range(k.C)),
+          V, f.name, slot, k.HYL, r, k.HXL, k.C))
     for i in range(k.K):
       line('      %s*(%s*)(&lds_%s[%d][0][0] + h_lds[%d]) = halo_%s[%d];' % (
-          halo_guard(k, i), V, f.name, (u + 1) % 2, i, f.name, i))
+          halo_guard(k, i), V, f.name, slot, i, f.name, i))
 
 
 def print_step(k, line, u, store):
   """One unrolled step of the plane loop; `store` prints what it computes and stores."""
-  line('    {  // unrolled step %d: output plane z, slot %d read, slot %d filled' % (
-      u, u % 2, (u + 1) % 2))
+  if k.ring:
+    line('    {  // unrolled step %d: output plane z, LDS slots %s filled' % (u, ', '.join(
+        '%s %d' % (f.name, lds_slot(k, f, u, f.phi + 1)) for f in k.shared)))
+  else:
+    line('    {  // unrolled step %d: output plane z, slot %d read, slot %d filled' % (
+        u, u % 2, (u + 1) % 2))
   if u:
     line('      if (n + %d >= steps) break;' % u)      # the whole workgroup leaves together
   line('      const i64 z = z0 + n + %d;' % (u - k.fill))
@@ -576,8 +683,8 @@ def print_entry(k, line, prologue):
   """The entry kernel: LDS slots, tile and chunk (`prologue`), the interior or the edge path."""
   line('GLOBAL WG_SIZE(%d) void %s(soda_hip_args a) {' % (k.threads, k.name))
   for f in k.shared:
-    line('  __attribute__((shared, aligned(16))) %s lds_%s[2][%d][%d];' % (
-        builtin_type(f.c_type), f.name, k.ROWS, k.PITCH))
+    line('  __attribute__((shared, aligned(16))) %s lds_%s[%d][%d][%d];' % (
+        builtin_type(f.c_type), f.name, k.lds_slots[f.name], k.ROWS, k.PITCH))
   line('  const int tid = __builtin_amdgcn_workitem_id_x();')
   prologue(k, line)
   line('  const bool interior = xs - %d >= 0 && xs + %d <= a.dims[0] && '
@@ -598,24 +705,29 @@ def table_entry(k):
                waves=k.waves, halo=[k.HXL, k.HXH, k.HYL, k.HYH], loaded_cells=loaded)
   if k.masks:
     entry['fields'] = len(k.stages)
+  if k.ring:
+    entry['lds_ring'] = [k.lds_slots[f.name] for f in k.shared]
   return entry
 
 
 def emit(spec, depth=1, waves=None, rows=None, lanes_x=None, chunk_planes=64,
-         max_period=16, vgpr_budget=250, fields=False):
+         max_period=16, vgpr_budget=250, fields=False, ring=False):
   """Returns (text, kernel table entry).  Without a shape: the first of
   shapes_by_loaded_cells that fits the register budget and the LDS cap.  `fields`: the
-  form over several outputs, each stored inside its own box."""
+  form over several outputs, each stored inside its own box.  `ring`: the plane-ring form,
+  every plane of an input that is read off the z axis in a ring of LDS slots."""
   if depth != 1:
     raise NotFusable('the LDS-plane form is depth 1')
-  several = bool(fields)
-  stages, fields = analyse(spec, several)
+  several, ring = bool(fields), bool(ring)
+  stages, fields = analyse(spec, several, ring)
   elem = specmod.ELEM_SIZE[specmod.tensor_c_types(spec)[spec['outputs'][0]]]
   # per output, the input it hands on unchanged (stored from the window, no cells of its own)
   through = [passed_through(spec, st) if several else None for st in stages]
-  fits = lambda shape: fit(fields, elem, through.count(None), shape, max_period, vgpr_budget)
-  k = first_fit(spec, several, fits) if waves is None else fits((waves, rows, lanes_x))
-  k.name, k.stages, k.fields, k.through = kernel_name(spec, several), stages, fields, through
+  fits = lambda shape: fit(fields, elem, through.count(None), shape, max_period, vgpr_budget,
+                           ring)
+  k = first_fit(spec, several, fits, ring) if waves is None else fits((waves, rows, lanes_x))
+  k.name, k.stages, k.fields, k.through = kernel_name(spec, several, ring), stages, fields, \
+      through
   k.shared, k.by_name = [f for f in fields if f.lds], {f.name: f for f in fields}
   k.index, k.elem, k.chunk_planes = tensor_index(spec), elem, chunk_planes
   k.fill = max(f.zhi - f.zlo + 1 for f in fields)

@@ -28,6 +28,11 @@ SWITCHES = (
            'for a 3-D program with two or three outputs that read inputs only '
            '(launched under a depth limit of 1: soda_hip_plan_set_max_depth)',
            '.ldsf', True, 'lds_fields'),
+    Switch('lds_ring', '--hip-lds-ring', 'hip_lds_ring',
+           'one fused depth-1 kernel with a ring of planes in LDS for a 3-D program '
+           'that reads an input off the z axis in several planes (mixed derivatives), '
+           'with one to three outputs (launched under a depth limit of 1: '
+           'soda_hip_plan_set_max_depth)', '.ldsr', True, 'lds_ring'),
 )
 BY_KEYWORD = {s.keyword: s for s in SWITCHES}
 

@@ -5,7 +5,9 @@ exception.  Needs no GPU and no hipcc.  Two trees that print the same lines gene
 same kernels; run it in both and diff the outputs (a refactoring of the generator's
 selection must give zero differing lines, the error lines included).
 
-The opt-in switches of generate() (fuse_outputs, lds_planes, lds_fields) are cases too, and
+The opt-in switches of generate() (fuse_outputs, lds_planes, lds_fields, lds_ring) are cases
+too (the cases of the first three are printed first and as they were before `lds_ring`
+existed, those with `lds_ring` after them: an older tree's output is a prefix-wise subset), and
 what is derived from them outside the generator has lines of its own: `host/...`, the sha256
 of the generated Python and C++ host texts per combination of switches, and `file/...`, the
 name of the prebuilt code object per combination build() uses.
@@ -94,10 +96,12 @@ for _, _, o in LITERAL:
   if o and o not in CROSSED:
     CROSSED.append(o)
 
-SWITCHES = ('fuse_outputs', 'lds_planes', 'lds_fields')
+SWITCHES = ('fuse_outputs', 'lds_planes', 'lds_fields', 'lds_ring')
+BEFORE_RING = SWITCHES[:3]
 # the samples the LDS-plane forms take, with the switches that give them their kernel
 LDS_SAMPLES = [(app, dict(lds_planes=True)) for app in lds3d.APPS] + [
     (app, lds3d_fields.switches(app)) for app in lds3d_fields.APPS]
+RING_SAMPLES = [(app, dict(lds_ring=True)) for app in entry.LDS_RING_APPS]
 HOST_PROGRAMS = ('jacobi2d', 'grad2d', 'grad3d', 'star3d', 'acoustic3d', 'deriv3d')
 HOST_CPP_SWITCHES = ('fuse_outputs', 'lds_fields')      # the keywords host_cpp.print_code took
 
@@ -192,7 +196,8 @@ def cases():
       yield 'crossed/%d/%s/%s' % (n, app, show(options)), \
           (lambda a=app: spec_of(a, None if a == 'denoise3d' else 31)), options
   # the opt-in switches: each alone and all together on every sample ...
-  together = [{n: True} for n in SWITCHES] + [{n: True for n in SWITCHES}]
+  together = [{n: True} for n in BEFORE_RING] + [{n: True for n in BEFORE_RING}]
+  with_ring = [dict(lds_ring=True), {n: True for n in SWITCHES}]
   for path in sorted(glob.glob(os.path.join(SAMPLES, '*.soda')) +
                      glob.glob(os.path.join(SAMPLES, 'extra', '*.soda'))):
     app = os.path.basename(path)[:-5]
@@ -211,6 +216,23 @@ def cases():
     make = lambda t=text: specmod.spec_from_stencil(frontend.loads(t))
     for on in [{}] + together:
       yield 'inline/%s/%s' % (key, show(on)), make, on
+  # `lds_ring`: alone and with the other three on every sample and program text, and its
+  # samples in every shape and at the iteration counts
+  for path in sorted(glob.glob(os.path.join(SAMPLES, '*.soda')) +
+                     glob.glob(os.path.join(SAMPLES, 'extra', '*.soda'))):
+    app = os.path.basename(path)[:-5]
+    for on in with_ring:
+      yield 'switch/%s/%s' % (app, show(on)), (lambda a=app: spec_of(a, None)), on
+  for app, on in RING_SAMPLES:
+    for shape in kernel_stream3d_lds.SHAPES:
+      yield 'lds_shape/%s/%s' % (app, show(shape)), (lambda a=app: spec_of(a, None)), \
+          dict(on, lds_shape=shape)
+    for iterate in (1, 2, 3, None):
+      yield 'lds_iterate/%s/%s' % (app, iterate), (lambda a=app, i=iterate: spec_of(a, i)), on
+  for key, text in inline_texts():
+    make = lambda t=text: specmod.spec_from_stencil(frontend.loads(t))
+    for on in with_ring:
+      yield 'inline/%s/%s' % (key, show(on)), make, on
 
 
 def digest(text):
@@ -223,7 +245,8 @@ def host_lines():
   show = lambda o: ','.join(sorted(o)) or '-'
   for app in HOST_PROGRAMS:
     spec = spec_of(app, None)
-    for on in combinations(SWITCHES):
+    for on in combinations(BEFORE_RING) + [dict(o, lds_ring=True)
+                                           for o in combinations(BEFORE_RING)]:
       out = io.StringIO()
       try:
         host_shim.print_code(spec, out, **on)
@@ -242,7 +265,8 @@ def host_lines():
       entry.FIELD1D_APPS + entry.RECT_APPS + entry.LDS3D_APPS + entry.LDS_FIELDS_APPS
   for apps, on in ((every, {}), (entry.FUSED_OUTPUT_APPS, dict(fuse_outputs=True)),
                    (entry.LDS3D_APPS, dict(lds_planes=True)),
-                   (entry.LDS_FIELDS_APPS, dict(lds_fields=True))):
+                   (entry.LDS_FIELDS_APPS, dict(lds_fields=True)),
+                   (entry.LDS_RING_APPS, {}), (entry.LDS_RING_APPS, dict(lds_ring=True))):
     for app in apps:
       yield 'file/%s/%s %s' % (app, show(on), os.path.basename(entry.blob_path(app, **on)))
 

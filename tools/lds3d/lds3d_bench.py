@@ -29,12 +29,19 @@ directory) or, where that was not run, from a run-time compile.
 outputs is not in the default schedule - and per-stage one launch per stage and iteration;
 every output is compared on its own box; no shape candidates are timed.
 
+`--ring`: the same protocol for the plane-ring form (kernel.generate's `lds_ring`; cross3d,
+skewcross3d, coupled3d from <app>.ldsr.hsaco, each at its own `iterate`), `lds` being the
+blob under set_max_depth(1).  Every shape of kernel_stream3d_lds.SHAPES that fits is a
+candidate (`--candidates 0`: all), the rule's shape first, so the best shape at or below
+64 KiB of LDS is among them; a candidate's every output is compared on its own box, and its
+fastest and slowest round are printed besides the median.
+
 Registers, LDS and scratch come from the code object's metadata.  `--static` prints the
 derived and the compiler's figures and times nothing (no GPU needed).
 
     python tools/lds3d/lds3d_bench.py [--apps APP ...] [--size W H D] [--sweeps K] [--repeats R]
                                 [--candidates N] [--static] [--build-candidates] [--out FILE]
-                                [--fields]
+                                [--fields | --ring]
 """
 import argparse
 import json
@@ -74,22 +81,24 @@ def static_line(kname, f):
       f['private_segment_fixed_size'], f['vgpr_spill_count'], f['sgpr_spill_count']))
 
 
-def fitting_shapes(spec):
+def fitting_shapes(spec, ring=False):
   """The shapes the generator would take, in its order, with their entries."""
   from soda_hip.codegen import kernel_stream2d, kernel_stream3d_lds
   from soda_hip.codegen import spec as specmod
   lowered = specmod.inline_pointwise(spec)
+  form = dict(fields=len(spec['outputs']) > 1, ring=True) if ring else {}
   out = []
-  for shape in kernel_stream3d_lds.shapes_by_loaded_cells(lowered):
+  for shape in kernel_stream3d_lds.shapes_by_loaded_cells(lowered, **form):
     try:
-      out.append((shape, kernel_stream3d_lds.emit(lowered, 1, *shape)[1]))
+      out.append((shape, kernel_stream3d_lds.emit(lowered, 1, *shape, **form)[1]))
     except kernel_stream2d.NotFusable:
       pass
   return out
 
 
-def candidate_path(entry, app, shape):
-  return os.path.join(entry.BLOBS, '%s.lds.%dx%dx%d.hsaco' % ((app,) + tuple(shape)))
+def candidate_path(entry, app, shape, ring=False):
+  return os.path.join(entry.BLOBS, '%s.lds%s.%dx%dx%d.hsaco' % (
+      (app, 'r' if ring else '') + tuple(shape)))
 
 
 def main():
@@ -108,20 +117,24 @@ def main():
                   help='compile the candidates\' code objects (hipcc) and exit: no GPU')
   ap.add_argument('--fields', action='store_true',
                   help='the form over several outputs (lds_fields) instead of lds_planes')
+  ap.add_argument('--ring', action='store_true',
+                  help='the plane-ring form (lds_ring) instead of lds_planes')
   ap.add_argument('--out', default=None)
   args = ap.parse_args()
-  assert args.sweeps >= 3
+  assert args.sweeps >= 3 and not (args.fields and args.ring)
   import __graft_entry__ as entry
   from soda_hip import frontend
   from soda_hip.codegen import kernel, spec as specmod
-  apps = args.apps or list(entry.LDS_FIELDS_APPS if args.fields else entry.LDS3D_APPS)
+  apps = args.apps or list(entry.LDS_FIELDS_APPS if args.fields else
+                           entry.LDS_RING_APPS if args.ring else entry.LDS3D_APPS)
   if args.fields:
     args.candidates = 0
+  on = dict(lds_ring=True) if args.ring else dict(lds_planes=True)    # of the candidates
   dims = tuple(args.size)
   shape = tuple(reversed(dims))
   lines = [
       'LDS-plane kernels for high-order 3-D stencils (kernel.generate: %s) against the'
-      % ('lds_fields' if args.fields else 'lds_planes'),
+      % ('lds_fields' if args.fields else 'lds_ring' if args.ring else 'lds_planes'),
       'per-stage schedule.  tools/lds3d/lds3d_bench.py: rounds of %d back-to-back sweeps between device'
       % args.repeats,
       'events, the two schedules alternating, %d untimed rounds, then the median (min .. max) of'
@@ -132,7 +145,7 @@ def main():
       'rates are algorithmic bytes x valid cell-updates over the measured time.  Register and LDS',
       'figures: code-object metadata (hipcc, gfx950).'] + ([] if args.fields else [
           'Shape candidates: (wavefronts, rows per lane, lanes per tile row), %d timed rounds each, '
-          'median.' % args.shape_rounds]) + ['']
+          'median%s.' % (args.shape_rounds, ' (min .. max)' if args.ring else '')]) + ['']
   for app in apps:
     spec = specmod.spec_from_stencil(frontend.load(entry.sample_path(app)))
     iterate = spec['iterate']
@@ -141,20 +154,23 @@ def main():
       blob = entry.blob_path(app, lds_fields=True)
       table = kernel.generate(spec, **switches.for_program(spec, lds_fields=True))[1]
     else:
-      blob = entry.blob_path(app, lds_planes=True)
-      table = kernel.generate(spec, lds_planes=True)[1]
+      blob = entry.blob_path(app, **on)
+      table = kernel.generate(spec, **on)[1]
     k = table[-1]
-    assert k['kind'] == 'fused' and \
-        k['name'] == app + ('_fused_k1lf' if args.fields else '_fused_k1l'), k
+    several = len(spec['outputs']) > 1
+    assert k['kind'] == 'fused' and k['name'] == app + (
+        '_fused_k1lf' if args.fields else
+        '_fused_k1r' + 'f' * several if args.ring else '_fused_k1l'), k
     stage_names = [e['name'] for e in table if e['kind'] == 'stage']
-    shapes = [] if args.fields else fitting_shapes(spec)[:max(1, args.candidates)]
+    shapes = [] if args.fields else fitting_shapes(spec, args.ring)
+    shapes = shapes[:max(1, args.candidates) if args.candidates or not args.ring else None]
     assert args.fields or (shapes[0][1]['tile'] == k['tile'] and
                            shapes[0][1]['block'] == k['block'])
     if args.build_candidates:
       for cand, _ in shapes[1:]:
-        text = kernel.generate(spec, lds_planes=True, lds_shape=cand)[0]
-        kernel.compile_to_code_object(text, candidate_path(entry, app, cand))
-        print('built', candidate_path(entry, app, cand))
+        text = kernel.generate(spec, lds_shape=cand, **on)[0]
+        kernel.compile_to_code_object(text, candidate_path(entry, app, cand, args.ring))
+        print('built', candidate_path(entry, app, cand, args.ring))
       continue
     elem = specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
     alg = specmod.algorithmic_bytes_per_update(spec)
@@ -172,7 +188,7 @@ def main():
       lines += static
       for cand, e in shapes[1:]:
         lines.append(static_line('  shape %s' % (cand,), static_figures(
-            candidate_path(entry, app, cand), k['name'])))
+            candidate_path(entry, app, cand, args.ring), k['name'])))
       continue
     import numpy as np
     from soda_hip.runtime import host
@@ -187,7 +203,8 @@ def main():
       d.upload(a.astype(dt))
       del a
     pin, pout = [d.ptr for d in din], [d.ptr for d in dout]
-    schedules = [('lds', 1 if args.fields else 0), ('per-stage', -1)]
+    fused_limit = 1 if args.fields or args.ring else 0
+    schedules = [('lds', fused_limit), ('per-stage', -1)]
     times = {name: [] for name, _ in schedules}
     launches = {}
 
@@ -214,15 +231,16 @@ def main():
       run(prog, name, limit, 1)
       results[name] = [d.download(shape, dt) for d, dt in zip(dout, prog.out_dtypes)]
     same = True
+    references, slices = [], []     # (the shape candidates below: per output, its box)
     for j, name in enumerate(spec['outputs']):
       lo, hi = specmod.iteration_boxes(spec, iterate)[-1][name]
       sl = tuple(slice(-lo[d], dims[d] - hi[d]) for d in (2, 1, 0))
       a, b = results['lds'][j][sl], results['per-stage'][j][sl]
       same = same and bool(np.array_equal(np.ascontiguousarray(a).view(np.uint8),
                                           np.ascontiguousarray(b).view(np.uint8)))
-      if j == 0:      # (the shape candidates below: one output, this slice)
-        reference, sl0 = np.ascontiguousarray(b).copy(), sl
-    sl = sl0
+      if j == 0 or args.ring:
+        references.append(np.ascontiguousarray(b).copy())
+        slices.append(sl)
     del results, a, b
     updates = specmod.valid_cells(spec, dims, iterate)
     med = {n: statistics.median(ts) for n, ts in times.items()}
@@ -246,38 +264,44 @@ def main():
                   shapes={})
     # the shape candidates, one at a time, each checked against the per-stage result
     for cand, e in shapes:
-      path = candidate_path(entry, app, cand)
+      path = candidate_path(entry, app, cand, args.ring)
       if cand == shapes[0][0]:
         other, how = prog, 'shipped'
       elif os.path.exists(path):
         other, how = host.open_program(blob=path, spec=spec), 'prebuilt'
       else:
         other, how = host.open_program(source=kernel.generate(
-            spec, lds_planes=True, lds_shape=cand)[0], spec=spec), 'run-time compile'
+            spec, lds_shape=cand, **on)[0], spec=spec), 'run-time compile'
       assert other.kernels[-1]['tile'] == e['tile'] and other.kernels[-1]['block'] == e['block']
       ts = []
       for r in range(1 + args.shape_rounds):
-        t = run(other, 'shape', 0, args.repeats)
+        t = run(other, 'shape', fused_limit, args.repeats)
         if r:
           ts.append(t['kernel_us'] / 1e3)
       assert launches['shape'] == [k['name']] * iterate
       for d in dout:
         d.zero()
-      run(other, 'shape', 0, 1)
-      got = np.ascontiguousarray(dout[0].download(shape, prog.out_dtypes[0])[sl])
-      ok = bool(np.array_equal(got.view(np.uint8), reference.view(np.uint8)))
-      del got
+      run(other, 'shape', fused_limit, 1)
+      ok = True
+      for j, (reference, sl) in enumerate(zip(references, slices)):
+        got = np.ascontiguousarray(dout[j].download(shape, prog.out_dtypes[j])[sl])
+        ok = ok and bool(np.array_equal(got.view(np.uint8), reference.view(np.uint8)))
+        del got
       f = static_figures(path if other is not prog else blob, k['name'])
-      lines.append('  shape %-12s tile %3d x %-3d %8.3f ms  %.2f x per-stage  loaded/stored %.3f  '
+      lines.append('  shape %-12s tile %3d x %-3d %8.3f ms%s  %.2f x per-stage  loaded/stored %.3f  '
                    '%s VGPRs, LDS %d B  %s%s' % (
                        cand, e['tile'][0], e['tile'][1], statistics.median(ts),
+                       ' (%.3f .. %.3f)' % (min(ts), max(ts)) if args.ring else '',
                        med['per-stage'] / statistics.median(ts),
                        e['loaded_cells'] / float(e['tile'][0] * e['tile'][1]) /
                        max(1, e['lds_planes']) if len(spec['inputs']) == 1 else
-                       e['lds_bytes'] / 2.0 / elem / (e['tile'][0] * e['tile'][1]),
+                       e['lds_bytes'] / float(sum(e.get('lds_ring', [2]))) / elem /
+                       (e['tile'][0] * e['tile'][1]),
                        f.get('vgpr_count', '?'), e['lds_bytes'], how,
                        '' if ok else '  OUTPUT DIFFERS'))
-      record['shapes'][str(cand)] = dict(ms=statistics.median(ts), identical=ok)
+      record['shapes'][str(cand)] = dict(ms=statistics.median(ts), min_ms=min(ts),
+                                         max_ms=max(ts), lds_bytes=e['lds_bytes'],
+                                         identical=ok)
       same = same and ok
       if other is not prog:
         other.close()
