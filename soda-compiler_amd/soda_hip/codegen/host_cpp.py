@@ -573,11 +573,13 @@ def print_code(spec, kernels, out, lowered=None, **on):
   w('  soda_hip_kernel kernels[%d];\n  const int n_kernels = fill_kernels(kernels);\n'
     % max(1, len(kernels)))
   w('  rc = soda_hip_plan_create(module, &program, kernels, n_kernels, &plan);\n')
-  if switches.depth_limit(on):
-    # generated with a switch that makes a fused kernel over all outputs: it is not in the
-    # default schedule, a depth limit admits it
+  limit, _ = switches.depth_limit_of(spec, on)
+  if limit:
+    # generated with a switch that makes a fused kernel over all outputs (limit 1) or the
+    # far-lane kernels of a program over several fields (their deepest depth): they are not
+    # in the default schedule, a depth limit admits them
     # (soda_hip_plan_set_max_depth)
-    w('  if (rc == 0) rc = soda_hip_plan_set_max_depth(plan, 1);\n')
+    w('  if (rc == 0) rc = soda_hip_plan_set_max_depth(plan, %d);\n' % limit)
   w('  if (rc == 0) {\n')
   w('    buffer_t* inputs[] = {%s};\n' % ', '.join('var_%s_buffer' % n for n in ins))
   w('    buffer_t* outputs[] = {%s};\n' % ', '.join('var_%s_buffer' % n for n in outs))

@@ -30,6 +30,8 @@ The unit holds
                         the same form with a ring of planes in LDS (<app>_fused_k1r, _k1rf),
                         only with `lds_ring=True` and only where no other form made a
                         depth-1 kernel;
+      2-D, x-neighbours beyond the next lane or windows above 12 rows: kernel_stream2d /
+                        kernel_fields2d with chained wave shifts, only with `far_lanes=True`;
   * `soda_hip_meta`, JSON describing the program and the kernel table, which
     libsoda_hip.so reads back from the loaded blob.
 
@@ -171,6 +173,11 @@ FIELDS1D_OPTIONS = STREAM1D_OPTIONS
 # the LDS-plane 3-D form (kernel_stream3d_lds; `lds_planes`): `lds_shape` = (wavefronts, rows
 # per lane, lanes per tile row) instead of the first shape that fits
 LDS3D_OPTIONS = ('lds_shape',)
+
+# the far-lane 2-D forms (`far_lanes`): kernel_stream2d / kernel_fields2d with x-neighbours up
+# to MAX_HOPS lanes away and windows of up to this many rows (a radius-8 window keeps 17 rows
+# and the 3 in flight; the row loop is unrolled by the period)
+FAR_MAX_PERIOD = 24
 
 # generator options of the fused 2-D forms that `generate` passes through:
 # those both forms understand, and those only the wave-pipelined form has
@@ -475,6 +482,7 @@ class Request:
     # far: an LDS-plane form is emitted only where they hold no fused depth-1 kernel
     self.on = {s.keyword: bool(on[s.keyword]) for s in switches.SWITCHES}
     self.meta_notes, self.made = {}, []
+    self.far = {}       # what `far_lanes` adds to the 2-D forms' arguments (generate())
     # one-pass programs with several outputs get the fields forms at depth 1 (opt-in:
     # profiles/r12_rect.txt); such a program is in nobody else's class
     fuse_outputs = self.on['fuse_outputs']
@@ -536,6 +544,69 @@ def fused_at_depths(req, notes, wanted, attempts_of):
       return
 
 
+_FAR_NOT_2D = 'not fused: the far-lane form handles 2-D programs'
+_FAR_NOT_CONCERNED = 'not concerned: every read within the neighbour lanes and %d rows'
+
+
+def far_lanes_arguments(req):
+  """What `far_lanes` adds to the arguments of kernel_stream2d.emit / kernel_fields2d.emit for
+  this request: `hops`, the lanes the lowered program reads away (MAX_HOPS at most: beyond,
+  emit refuses as ever), and FAR_MAX_PERIOD - for a 2-D program that those forms refuse a
+  depth-1 kernel today for an x offset beyond the neighbour lane or for a window above their
+  period limit; {} for every other program, whose text then stays what it is.  Leaves in
+  req.meta_notes why a program is not in the class; far_lanes_note() says the rest.
+  generate() calls it once, the families read the result as `req.far`."""
+  if not req.on['far_lanes']:
+    return {}
+  key = switches.BY_KEYWORD['far_lanes'].note
+  spec = req.spec
+  if spec['dim'] != 2:
+    req.meta_notes[key] = _FAR_NOT_2D
+    return {}
+  limit = kernel_stream2d.DEFAULT_MAX_PERIOD
+  hops = max([1] + [-(-abs(rel[0]) // req.strip['cols'])
+                    for stage in spec['stages'] for _, rel in stage['loads']])
+  try:
+    fields = kernel_stream2d.multi_field(spec) or kernel_stream2d.rectangular(spec)
+    insts, _ = kernel_stream2d.build_pipeline(spec, 1, req.strip['prefetch'], fields=fields)
+    rows = max(inst.keep for inst in insts)
+  except kernel_stream2d.NotFusable:
+    rows = 0          # no 2-D form takes it, whatever its reach: refused as ever
+  if hops == 1 and rows <= req.options.get('max_period', limit):
+    req.meta_notes[key] = _FAR_NOT_CONCERNED % limit
+    return {}
+  if kernel_stream2d.rectangular(spec) and not req.rect:
+    req.meta_notes[key] = _NOT_RECT[1]
+    return {}
+  return dict(hops=min(hops, kernel_stream2d.MAX_HOPS), max_period=FAR_MAX_PERIOD)
+
+
+def far_lanes_note(req, notes):
+  """The entry `far_lanes` of soda_hip_meta for a program in the switch's class: the depth-1
+  kernel made, or why there is none."""
+  key = switches.BY_KEYWORD['far_lanes'].note
+  if not req.far:
+    return
+  made = [e['name'] for e in req.made if e['kind'] == 'fused' and e['depth'] == 1]
+  why = [n[len('depth 1 not fused: '):] for n in notes if n.startswith('depth 1 not fused: ')]
+  req.meta_notes[key] = made[0] if made else 'not fused: %s' % (why + ['no 2-D form takes it'])[0]
+
+
+def far_lanes_depth_limit(spec):
+  """The depth limit under which the entry points of a `far_lanes` product run.  The
+  launcher admits fused kernels over several fields only under a positive limit
+  (csrc/schedule.cpp, plans_fused), so a program over several fields that the switch gives
+  its kernels runs under the depth of the deepest of them; 0, no limit, for every other
+  program - a single-array program's kernels are in the default schedule, and a multi-field
+  program outside the switch's class runs as it does without the switch."""
+  if spec['dim'] != 2 or not kernel_stream2d.multi_field(spec):
+    return 0
+  text, table = generate(spec, far_lanes=True)
+  made = kernel_common.read_meta_from_source(text).get(switches.BY_KEYWORD['far_lanes'].note)
+  depths = [k['depth'] for k in table if k['kind'] == 'fused']
+  return max(depths) if depths and made in [k['name'] for k in table] else 0
+
+
 def fields2d_kernels(req, notes):
   """Multi-field 2-D programs: kernel_fields2d at each depth; rectangular ones, when
   generate() was asked to fuse their outputs, at depth 1."""
@@ -544,8 +615,9 @@ def fields2d_kernels(req, notes):
     notes.append(req.rect_refusal)
   if spec['dim'] != 2 or not (kernel_stream2d.multi_field(spec) or req.rect):
     return
+  far = req.far
   yield from fused_at_depths(req, notes, [1] if req.rect else chain_depths(req), lambda depth: [
-      (kernel_fields2d.emit, dict(req.strip, **form_options('fields2d', req.options)))])
+      (kernel_fields2d.emit, dict(req.strip, **dict(far, **form_options('fields2d', req.options))))])
 
 
 def fields3d_kernels(req, notes):
@@ -611,12 +683,13 @@ def stream2d_depths(req):
   return wanted
 
 
-def stream2d_single(req, depth, strip, notes):
-  """The single-wave kernel of this depth (kernel_stream2d), or None with a note."""
+def stream2d_single(req, depth, strip, notes, far):
+  """The single-wave kernel of this depth (kernel_stream2d), or None with a note.  far: what
+  far_lanes_arguments() adds to the form's arguments."""
   # the memory-bound depths store around the caches when a launch's box
   # does not fit the Infinity Cache (kernel_stream2d.emit: nontemporal)
   options = dict({'nontemporal': 4} if depth <= NT_AUTO_MAX_DEPTH_2D else {},
-                 **form_options('stream2d', req.options))
+                 **dict(far, **form_options('stream2d', req.options)))
   # ... and where no STAGE is read across lanes (depth 1 of the samples) their
   # strips do not overlap at all (align='exact': whole 128-byte lines in and
   # out, the seam columns from one extra vector load per row and side)
@@ -709,6 +782,7 @@ def stream2d_kernels(req, notes):
   spec = req.spec
   if spec['dim'] != 2 or kernel_stream2d.multi_field(spec) or req.rect:
     return
+  far = req.far
   for depth in stream2d_depths(req):
     strip = dict(req.strip)
     if 'align' not in req.options:
@@ -721,13 +795,14 @@ def stream2d_kernels(req, notes):
           arithmetic_weight(spec) <= ALIGN_FULL_MAX_WEIGHT) else 'none'
     single = piped = None
     if req.groups <= 1 or depth < WAVE_PIPELINE_MIN_DEPTH:
-      single = stream2d_single(req, depth, strip, notes)
+      single = stream2d_single(req, depth, strip, notes, far)
     if want_piped(req, depth, single):
       piped = stream2d_piped(req, depth, strip, notes)
       if piped is None and single is None and req.groups > 1:
         # asked for by a number of wavefronts and refused: the single-wave form after all
         single, error = first_fusable(spec, depth, [
-            (kernel_stream2d.emit, dict(strip, **form_options('stream2d', req.options)))])
+            (kernel_stream2d.emit,
+             dict(strip, **dict(far, **form_options('stream2d', req.options))))])
         if single is None:
           notes.append('depth %d not fused: %s' % (depth, error))
     if piped is not None or single is not None:
@@ -915,8 +990,8 @@ FAMILIES = (fields2d_kernels, fields3d_kernels, fields1d_kernels, stream1d_kerne
 
 def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
              fused=True, depths=None, inline=True, wave_groups=None,
-             fuse_outputs=False, lds_planes=False, lds_fields=False, lds_ring=False,
-             **fused_options):
+             fuse_outputs=False, lds_planes=False, lds_fields=False, far_lanes=False,
+             lds_ring=False, **fused_options):
   """Returns (kernel text, kernel table).  `depths` overrides the default set
   of fused depths (depth 1 is always included: the scheduler needs it).
   `fuse_outputs`: a one-pass 2-D / 3-D program with several outputs that is not
@@ -943,7 +1018,15 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   under a depth limit of 1.  A program that reads every input off the z axis in at most one
   plane is not concerned, so the three LDS switches concern disjoint programs and may be
   given together.  Every other program keeps its table and, apart from the entry `lds_ring`
-  of soda_hip_meta, its text."""
+  of soda_hip_meta, its text.
+  `far_lanes`: a 2-D program that kernel_stream2d / kernel_fields2d refuse a depth-1 kernel
+  because it reads an x-neighbour beyond the next lane (float stars of radius 5 and up,
+  double ones of radius 3 and up) or keeps a window above 12 rows gets the same forms with
+  chained wave shifts (`hops`, up to kernel_stream2d.MAX_HOPS lanes) and a rotation period of
+  up to FAR_MAX_PERIOD, at the family's usual depths and under the usual names
+  `<app>_fused_k<d>`, in the default schedule; a rectangular one with `fuse_outputs` as well.
+  Every other program keeps its table and, apart from the entry `far_lanes` of
+  soda_hip_meta, its text."""
   # kernels are generated from the LOWERED program (pointwise-only locals folded
   # into their readers); the blob is still identified by the source program
   source = spec
@@ -960,12 +1043,15 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   notes = []
   req = Request(spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
                 fused_options, dict(fuse_outputs=fuse_outputs, lds_planes=lds_planes,
-                                    lds_fields=lds_fields, lds_ring=lds_ring))
+                                    lds_fields=lds_fields, far_lanes=far_lanes,
+                                    lds_ring=lds_ring))
+  req.far = far_lanes_arguments(req)
   for family in FAMILIES if fused else ():
     for ftext, entry in family(req, notes):
       parts.append(ftext)
       table.append(annotate_cost(entry, spec))
       req.made.append(entry)
+  far_lanes_note(req, notes)
   if notes:
     parts.append(''.join('// %s\n' % n for n in notes))
   extra = dict(program_hash=kernel_common.program_hash(source),

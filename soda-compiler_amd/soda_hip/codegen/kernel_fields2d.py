@@ -37,7 +37,8 @@ file: the kernels compile with no SGPR parked in VGPR lanes.
 
 from . import spec as specmod
 from .kernel_common import builtin_type, cell_assignment, tensor_index
-from .kernel_stream2d import (LANES, WAVES_PER_BLOCK, NotFusable, build_pipeline,
+from .kernel_stream2d import (DEFAULT_MAX_PERIOD, LANES, WAVES_PER_BLOCK, NotFusable,
+                              build_pipeline, check_reach,
                               estimated_vgprs, geometry, kernel_name, lane_operand,
                               multi_field, rectangular, rotation_period, set_first_steps,
                               slot)
@@ -71,10 +72,11 @@ def pack_extras(extras):
   return words
 
 
-def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
-         vgpr_budget=244, waves_per_eu=0, skip_fill=1):
+def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=DEFAULT_MAX_PERIOD,
+         vgpr_budget=244, waves_per_eu=0, skip_fill=1, hops=1):
   """Returns (text, kernel table entry) for one fused depth of a multi-field program, or
-  for depth 1 of a rectangular one (kernel_stream2d.rectangular)."""
+  for depth 1 of a rectangular one (kernel_stream2d.rectangular).  hops: as in
+  kernel_stream2d.emit."""
   rect = depth == 1 and rectangular(spec)
   if not multi_field(spec) and not rect:
     raise NotFusable('fields2d handles programs whose outputs feed their inputs pairwise')
@@ -94,11 +96,7 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
   C = cols
   insts, _ = build_pipeline(spec, depth, prefetch, fields=True)
   geo = geometry(spec, depth, cols, chunk_rows, 'none')
-  for inst in insts:
-    for src, rel, _ in inst.reads:
-      if abs(rel[0]) > cols:
-        raise NotFusable('x offset %d exceeds the %d columns a lane holds'
-                         % (rel[0], cols))
+  check_reach(insts, cols, hops)
   finals = [inst for inst in insts if inst.final]
   # (an output that a later stage reads lives in its window, `keep` rows, and is stored
   # from the newest one; the others go to HBM straight from a row of temporaries)

@@ -32,6 +32,11 @@ from .kernel_common import builtin_type, cell_assignment, device_expr, tensor_in
 
 WAVES_PER_BLOCK = 4
 LANES = 64
+# lanes an x-neighbour may lie away in the far-lane form (emit's `hops`): every lane is one
+# more wave shift per operand and one more lane of halo on that side of the strip
+MAX_HOPS = 4
+# rows the row loop is unrolled by at most (emit's `max_period`) unless the caller says otherwise
+DEFAULT_MAX_PERIOD = 12
 
 
 class NotFusable(Exception):
@@ -201,13 +206,60 @@ def rotation_period(insts, max_period):
   return best[1]
 
 
+def far_hops(insts, cols):
+  """Lanes away the farthest x-neighbour of the pipeline lies (lane_operand): 1 for every
+  program the neighbour-lane forms take."""
+  return max([1] + [-(-abs(rel[0]) // cols) for inst in insts for _, rel, _ in inst.reads])
+
+
+def check_reach(insts, cols, hops):
+  if not 1 <= hops <= MAX_HOPS:
+    raise ValueError('hops: %r' % (hops,))
+  for inst in insts:
+    for src, rel, _ in inst.reads:
+      if abs(rel[0]) > hops * cols:
+        raise NotFusable('x offset %d exceeds the %d columns a lane holds'
+                         % (rel[0], cols))
+
+
 def estimated_vgprs(insts, cols):
   """Every retained row costs `cols` VGPRs per lane (2 x for 8-byte types), the edge
   columns of seam-free strips along with them; past ~224 the kernel drops below two
   waves per SIMD and then spills."""
   return sum(inst.keep * (cols + sum(getattr(inst, 'edges', {}).values())) *
              max(1, specmod.ELEM_SIZE[inst.c_type] // 4) for inst in insts) + \
-      4 * cols + 16
+      4 * cols + 16 + far_vgprs(insts, cols)
+
+
+def far_vgprs(insts, cols):
+  """What reads beyond the neighbour lane keep alive while an instance's row is computed: 0
+  for a program without them.  A wave shift folds into the operation that consumes it, a
+  chain of shifts does not: every link is a move into a register of its own, shared by the
+  cells that read the same column.  Per instance, in 32-bit words: N, the distinct links of
+  its chains of two shifts and more; P, the reads of its cells that end such a chain; one row
+  of results twice over (the sums in flight and the row being put together for its store).
+  The instances of a step run one after the other, so the costliest one counts.  The weights
+  are FITTED to what the compiler allots over the window rows (hipcc 7.2, gfx950; extra over
+  the estimate without this term, depth 1 / 2): star2d N 16 P 20 +29 / +49, dstar2d and
+  acoustic2d N 16 P 12 +15 / +16 and +18 / +38, skewfar2d N 15 P 6 +14 / +6 - the radius-8
+  float star at depth 2, 241 VGPRs against an estimate of 192 without it, is the case that
+  sets them.  tests/test_far2d_codegen.py holds every shipped kernel to its estimate."""
+  worst = 0
+  for inst in insts:
+    links, operands = {}, {}
+    for src, rel, _ in inst.reads:
+      words = max(1, specmod.ELEM_SIZE[src.c_type] // 4)
+      for j in range(rel[0], rel[0] + cols):
+        lanes = abs(j // cols)
+        if lanes >= 2:
+          operands[id(src), rel, j] = words
+          for link in range(1, lanes + 1):
+            links[id(src), rel[1], j % cols, j < 0, link] = words
+    if links:
+      row = cols * max(1, specmod.ELEM_SIZE[inst.c_type] // 4)
+      worst = max(worst, sum(links.values()) + -(-5 * sum(operands.values()) // 4) +
+                  2 * row + 1)
+  return worst
 
 
 def set_first_steps(insts, y_lo):
@@ -235,26 +287,30 @@ def slot(inst, u, back):
 
 def lane_operand(reader, src, rel, u, c, cols):
   """Cell (c + rel[0]) of the row of `src` that `reader` reads at rel: a register of
-  the lane's own window, or the neighbouring lane's through a DPP wave shift."""
+  the lane's own window, or a lower / higher lane's through DPP wave shifts - one per lane
+  the cell is away (`hops` of emit: beyond the neighbour lane only in the far-lane form)."""
   back = reader.lag - src.lag - rel[1]
   assert 0 <= back < src.keep, (reader.ident, src.ident, rel, back, src.keep)
   row = '%s[%d]' % (src.ident, slot(src, u, back))
   j = c + rel[0]
-  if 0 <= j < cols:
-    return '%s[%d]' % (row, j)
-  if j < 0:
-    return 'from_lane_below(%s[%d])' % (row, cols + j)
-  return 'from_lane_above(%s[%d])' % (row, j - cols)
+  text = '%s[%d]' % (row, j % cols)
+  for _ in range(abs(j // cols)):       # ceil(-j / cols) lanes below, j // cols above
+    text = 'from_lane_%s(%s)' % ('below' if j < 0 else 'above', text)
+  return text
 
 
 def kernel_name(spec, depth):
   return '%s_fused_k%d' % (spec['app_name'], depth)
 
 
-def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
+def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=DEFAULT_MAX_PERIOD,
          vgpr_budget=244, waves_per_eu=0, skip_fill=1, nontemporal=0, align='none',
-         steady=None, stage_edges=0, stream_wgs=None):
+         steady=None, stage_edges=0, stream_wgs=None, hops=1):
   """Returns (text, kernel table entry) for one fused depth.
+
+  hops: how many lanes away an x-neighbour may lie (1 .. MAX_HOPS; lane_operand chains one
+  wave shift per lane).  Strips, halo lanes and store ranges follow geometry() whatever the
+  reach; only the seam-free strips (align='exact') are written for the neighbour lane.
 
   steady (default: on for depth <= 2, the memory-bound kernels): the rows of a chunk
   whose loads need no clamping and whose results are all stored run in a loop of their
@@ -279,12 +335,10 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
   insts, final = build_pipeline(spec, depth, prefetch)
   geo = geometry(spec, depth, cols, chunk_rows, align)
   C = cols
-  for inst in insts:
-    for src, rel, _ in inst.reads:
-      if abs(rel[0]) > cols:
-        raise NotFusable('x offset %d exceeds the %d columns a lane holds'
-                         % (rel[0], cols))
+  check_reach(insts, cols, hops)
   exact = align == 'exact'
+  if exact and far_hops(insts, cols) > 1:
+    raise NotFusable('seam-free strips: a read beyond the neighbour lane')
   # the steady-state loop without any branch (round 4): the row's store is a raw buffer
   # store whose lane offset is out of range in lanes that store nothing (halo lanes of
   # overlapping strips), a scheduling fence per row, loaded rows kept packed - see emit_body
@@ -321,6 +375,13 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
   set_first_steps(insts, geo['y_lo'])
   name = kernel_name(spec, depth)
   C = cols
+  # The kernels only the far-lane form makes unroll long rows of many terms, and the
+  # per-column conditions of the two rare paths (a load at the array's edge, a lane that
+  # stores part of its columns), which do not change along the row loop, would each stay a
+  # 64-bit lane mask in a pair of SGPRs across it: more pairs than the SGPR file has left,
+  # so the compiler parked 16 to 56 SGPRs in VGPR lanes.  As in kernel_fields2d the per-lane
+  # operand goes through an empty asm there, and the conditions are recomputed where used.
+  lean = far_hops(insts, cols) > 1 or period > DEFAULT_MAX_PERIOD
   L = final.lag
   vec_bytes = C * elem
   T_in = builtin_type(in_type)
@@ -346,6 +407,13 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
             % (T_out, vec_out, C, elem))
   emit_line('typedef unsigned soda_u2 __attribute__((ext_vector_type(2)));')
   emit_line('typedef unsigned soda_u4 __attribute__((ext_vector_type(4)));')
+  if lean:
+    emit_line('template <typename T> DEV void %s_opaque(T& v) { asm volatile("" : "+v"(v)); }'
+              % name)
+    # ... and a row number goes through one as the scalar it is: otherwise the row addresses
+    # of all `period` unrolled steps become induction variables of the loop, a pair of SGPRs
+    # each for loads and for stores
+    emit_line('DEV void %s_opaque_row(i64& v) { asm volatile("" : "+s"(v)); }' % name)
   # nontemporal: 1 = loads, 2 = stores, 4 = the stores of launches whose box does not
   # fit the Infinity Cache (kernel_common.NT_STREAMING_BYTES), as an instantiation of
   # the steady interior path chosen per launch.  Per launch at 16384^2, stores always /
@@ -446,8 +514,9 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
           emit_line('      %s{  // load row head+%d of %s' % (
               'if (head + %d <= load_last) ' % u if steady and not calm else '', u,
               inst.tensor))
-          emit_line('        i64 row = head + %d;%s' % (
-              u, '' if calm else ' if (row > H - 1) row = H - 1;'))
+          emit_line('        i64 row = head + %d;%s%s' % (
+              u, '' if calm else ' if (row > H - 1) row = H - 1;',
+              ' %s_opaque_row(row);' % name if lean else ''))
           emit_line('        const %s* p = g_%s + row * W + x;' % (
               builtin_type(inst.c_type), inst.tensor))
           emit_line('        if (INTERIOR) {')
@@ -461,10 +530,12 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
           for c in range(0 if inst.packed else C):
             emit_line('          %s[%d][%d] = v[%d];' % (inst.ident, s, c, c))
           emit_line('        } else {')
+          if lean:
+            emit_line('          i64 xe = x; %s_opaque(xe);' % name)
           for c in range(C):
-            emit_line('          %s[%d][%d] = (x + %d >= 0 && x + %d < W) ? p[%d] : '
-                      '(%s)0;' % (inst.ident, s, c, c, c, c,
-                                  builtin_type(inst.c_type)))
+            emit_line('          %s[%d][%d] = (%s + %d >= 0 && %s + %d < W) ? p[%d] : '
+                      '(%s)0;' % (inst.ident, s, c, 'xe' if lean else 'x', c,
+                                  'xe' if lean else 'x', c, c, builtin_type(inst.c_type)))
           emit_line('        }')
           for side, k in [('lo', k) for k in range(inst.edges['lo'])] + \
               [('hi', k) for k in range(inst.edges['hi'])]:
@@ -506,9 +577,13 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
                             load_edge, emit_line, '      ')
         if inst.final:
           emit_line('      {  // store row head+%d-%d' % (u, L))
-          emit_line('        const i64 y = head + %d;' % (u - L))
+          emit_line('        %si64 y = head + %d;%s' % (
+              '' if lean else 'const ', u - L, ' %s_opaque_row(y);' % name if lean else ''))
           emit_line('        %s{' % ('' if calm else 'if (y >= y0 && y < y1) '))
           emit_line('          %s* q = g_out + y * W + x;' % T_out)
+          xq = 'xq' if lean else 'x'
+          if lean:
+            emit_line('          i64 xq = x; %s_opaque(xq);' % name)
           if calm and flat:
             # !RAGGED (decided once per strip): a lane stores its whole vector or nothing -
             # ONE raw buffer store on the row, the lane's offset out of range where it
@@ -526,11 +601,12 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
                       '(int)(W * %d), 0x27000), st_voff, 0, %s);' % (
                           bits[0], bits[1], elem, 'NT ? 2 : 0' if nt_auto else
                           '2' if nontemporal & 2 else '0'))
-            emit_line('          } else if (x >= st_lo && x + %d <= st_hi) {' % C)
+            emit_line('          } else if (%s >= st_lo && %s + %d <= st_hi) {' % (xq, xq, C))
           elif calm:
-            emit_line('          if (RAGGED ? (x >= st_lo && x + %d <= st_hi) : st_full) {' % C)
+            emit_line('          if (RAGGED ? (%s >= st_lo && %s + %d <= st_hi) : st_full) {'
+                      % (xq, xq, C))
           else:
-            emit_line('          if (x >= st_lo && x + %d <= st_hi) {' % C)
+            emit_line('          if (%s >= st_lo && %s + %d <= st_hi) {' % (xq, xq, C))
           emit_line('            %s v;' % vec_out)
           for c in range(C):
             emit_line('            v[%d] = out_row[%d];' % (c, c))
@@ -543,8 +619,8 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
             emit_line('            *(%s*)q = v;' % vec_out)
           emit_line('          } else %s{' % ('if (RAGGED) ' if calm else ''))
           for c in range(C):
-            emit_line('            if (x + %d >= st_lo && x + %d < st_hi) q[%d] = '
-                      'out_row[%d];' % (c, c, c, c))
+            emit_line('            if (%s + %d >= st_lo && %s + %d < st_hi) q[%d] = '
+                      'out_row[%d];' % (xq, c, xq, c, c, c))
           emit_line('          }')
           emit_line('        }')
           emit_line('      }')
@@ -588,7 +664,13 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=12,
   emit_line('GLOBAL WG_SIZE(%d)%s void %s(soda_hip_args a) {'
             % (WAVES_PER_BLOCK * LANES, occupancy, name))
   emit_line('  const int lane = lane_id();')
-  emit_line('  const int wave = __builtin_amdgcn_workitem_id_x() >> 6;')
+  if lean:
+    # (the wavefront's number as the scalar it is: the strip's origin, its chunk and which of
+    # the strip variants it runs are then wave-uniform, and their branches keep no lane masks)
+    emit_line('  const int wave = __builtin_amdgcn_readfirstlane('
+              '__builtin_amdgcn_workitem_id_x() >> 6);')
+  else:
+    emit_line('  const int wave = __builtin_amdgcn_workitem_id_x() >> 6;')
   emit_line('  const i64 x_origin = a.box_lo[0] - a.box_lo[0] %% %d;' % geo['origin_align'])
   # (Re-dealing the workgroups so that every XCD - ids b and b + 8 share one L2 - works
   # on a contiguous run of tiles was measured: jacobi2d 16384^2 depths 12 / 8 and blur

@@ -28,6 +28,13 @@ SWITCHES = (
            'for a 3-D program with two or three outputs that read inputs only '
            '(launched under a depth limit of 1: soda_hip_plan_set_max_depth)',
            '.ldsf', True, 'lds_fields'),
+    Switch('far_lanes', '--hip-far-lanes', 'hip_far_lanes',
+           'the fused 2-D kernels for a program that reads an x-neighbour beyond the next '
+           'lane or keeps a window above 12 rows (float stars of radius 5 and up, double '
+           'ones of radius 3 and up): the same forms with chained wave shifts.  The kernels '
+           'of a program over one array run in the default schedule; a program over several '
+           'fields is launched under the depth limit of its deepest kernel '
+           '(soda_hip_plan_set_max_depth)', '.far', False, 'far_lanes'),
     Switch('lds_ring', '--hip-lds-ring', 'hip_lds_ring',
            'one fused depth-1 kernel with a ring of planes in LDS for a 3-D program '
            'that reads an input off the z axis in several planes (mixed derivatives), '
@@ -59,6 +66,20 @@ def depth_limit_flags(on):
 def depth_limit(on):
   """Do these switches need the depth limit that admits a kernel over several outputs?"""
   return bool(depth_limit_flags(on))
+
+
+def depth_limit_of(spec, on):
+  """The depth limit the entry points generated for `spec` with the switches `on` set before
+  they run, and the flags that ask for it: (0, []) for none.  1 where a switch makes a fused
+  kernel over several outputs; under `far_lanes`, for a program over several fields that the
+  switch gives its kernels, the depth of the deepest (kernel.far_lanes_depth_limit)."""
+  if depth_limit(on):
+    return 1, depth_limit_flags(on)
+  if on.get('far_lanes'):
+    from . import kernel
+    limit = kernel.far_lanes_depth_limit(spec)
+    return limit, [BY_KEYWORD['far_lanes'].flag] if limit else []
+  return 0, []
 
 
 def keyword_text(on):

@@ -529,8 +529,9 @@ def app_test(spec, blob, dims, source=None, iterate=None, **on):
   iterate = spec['iterate'] if iterate is None else iterate
   dims = [int(v) for v in list(dims)[:spec['dim']]]
   prog = open_program(blob=blob, source=source, spec=spec, **on)
-  if switches.depth_limit(on):      # a fused kernel over several outputs: under a depth limit
-    prog.set_max_depth(1)
+  limit, _ = switches.depth_limit_of(spec, on)
+  if limit:       # fused kernels the default schedule does not hold: under a depth limit
+    prog.set_max_depth(limit)
   try:
     inputs = reference_init(spec, dims)
     shape = inputs[0].shape

@@ -1,0 +1,218 @@
+#!/usr/bin/env python3
+"""High-order 2-D stencils (star2d and skewfar2d at 16384 x 16384, dstar2d and acoustic2d at
+8192 x 8192, `--iterate` iterations): the far-lane fused kernels (kernel.generate's
+`far_lanes`; kernel_stream2d / kernel_fields2d with chained wave shifts) against the
+per-stage schedule, on one GPU, both from the code object __graft_entry__.build() makes with
+the switch (<app>.far.hsaco), in one process, alternating - the protocol of
+tools/lds3d/lds3d_bench.py.
+
+default   = what a `--hip-far-lanes` product runs: the blob's default schedule, for
+            acoustic2d, whose kernels are over several fields, under the depth limit its
+            generated entry points set (switches.depth_limit_of; the row is then labelled
+            `limit N`): the launcher admits such kernels only under a limit;
+depth d   = the same sweep with its split fixed to launches of <app>_fused_k<d> only
+            (soda_hip_plan_set_split), for every fused depth of the table;
+per-stage = the same blob under set_max_depth(-1): one launch per stage and iteration, one
+            cell per work-item, every operand a global load - what these programs run
+            without the switch.
+
+First every schedule runs once and its outputs are compared with the per-stage outputs bit
+for bit on every output's box, at the size timed: nothing is timed unless they are identical.
+A round times `--repeats` back-to-back sweeps of one schedule between device events and takes
+their mean; the rounds of the schedules alternate, the first `--warmup` rounds are dropped,
+and the median, the fastest and the slowest of the `--sweeps` timed rounds are reported, per
+sweep, per launch and per iteration.  A schedule is FASTER than per-stage if its median is
+below the per-stage median by more than the spread (the larger max - min of the two).
+
+Registers and spills come from the code object's metadata, code sizes from its symbol table.
+
+    python tools/far2d/far2d_bench.py [--apps APP ...] [--iterate N] [--sweeps K] [--repeats R]
+                                      [--out FILE]
+"""
+import argparse
+import json
+import os
+import re
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+for p in (ROOT, os.path.join(ROOT, 'soda-compiler_amd'), os.path.join(ROOT, 'tools')):
+  if p not in sys.path:
+    sys.path.insert(0, p)
+
+READELF = '/opt/rocm/lib/llvm/bin/llvm-readelf'
+SIZES = {4: (16384, 16384), 8: (8192, 8192)}      # by element size: float, double
+
+
+def static_figures(blob, kname):
+  """VGPRs, SGPRs, scratch and spills of one kernel from the code object's notes."""
+  if not (os.path.exists(READELF) and os.path.exists(blob)):
+    return {}
+  notes = subprocess.check_output([READELF, '--notes', blob]).decode()
+  for block in notes.split('- .agpr_count'):
+    m = re.search(r'\.name:\s+(\S+)', block)
+    if m and m.group(1) == kname:
+      return {k: int(re.search(r'\.%s:\s+(\d+)' % k, block).group(1))
+              for k in ('vgpr_count', 'sgpr_count', 'private_segment_fixed_size',
+                        'vgpr_spill_count', 'sgpr_spill_count')}
+  return {}
+
+
+def code_bytes(blob, kname):
+  """Size of one kernel's code from the code object's symbol table."""
+  symbols = subprocess.check_output([READELF, '-s', blob]).decode()
+  m = re.search(r'^\s*\d+:\s+[0-9a-f]+\s+(\d+)\s+FUNC\s.*\s%s$' % re.escape(kname), symbols, re.M)
+  return int(m.group(1)) if m else 0
+
+
+def main():
+  ap = argparse.ArgumentParser(description=__doc__,
+                               formatter_class=argparse.RawDescriptionHelpFormatter)
+  ap.add_argument('--apps', nargs='+', default=None,
+                  help='default: star2d dstar2d skewfar2d acoustic2d (far_lanes)')
+  ap.add_argument('--iterate', type=int, default=24,
+                  help='iterations per sweep: a multiple of every fused depth')
+  ap.add_argument('--sweeps', type=int, default=7, help='timed rounds per schedule (>= 3)')
+  ap.add_argument('--warmup', type=int, default=2, help='untimed rounds per schedule')
+  ap.add_argument('--repeats', type=int, default=3, help='sweeps per round')
+  ap.add_argument('--out', default=None)
+  args = ap.parse_args()
+  assert args.sweeps >= 3
+  import numpy as np
+  import __graft_entry__ as entry
+  from soda_hip import frontend
+  from soda_hip.codegen import kernel, switches, spec as specmod
+  from soda_hip.runtime import host
+  apps = args.apps or list(entry.FAR_LANES_APPS)
+  iterate = args.iterate
+  lines = [
+      'Far-lane fused 2-D kernels (kernel.generate: far_lanes) against the per-stage schedule of',
+      'the same code object.  tools/far2d/far2d_bench.py: outputs of every schedule compared bit for',
+      'bit with the per-stage outputs first; then rounds of %d back-to-back sweeps between device'
+      % args.repeats,
+      'events, the schedules alternating, %d untimed rounds, then the median (min .. max) of %d'
+      % (args.warmup, args.sweeps),
+      'timed rounds.  A sweep = %d iterations.  FASTER: the medians differ by more than the spread'
+      % iterate,
+      '(the larger max - min of the two series).  Register figures: code-object metadata (hipcc,',
+      'gfx950).', '']
+  for app in apps:
+    spec = specmod.spec_from_stencil(frontend.load(entry.sample_path(app)))
+    blob = entry.blob_path(app, far_lanes=True)
+    table = kernel.generate(spec, far_lanes=True)[1]
+    fused = [k for k in table if k['kind'] == 'fused']
+    stage_names = [e['name'] for e in table if e['kind'] == 'stage']
+    assert fused and all(iterate % k['depth'] == 0 for k in fused), (app, iterate)
+    elem = specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
+    dims = SIZES[elem]
+    shape = tuple(reversed(dims))
+    limit, _ = switches.depth_limit_of(spec, dict(far_lanes=True))
+    default = 'limit %d' % limit if limit else 'default'
+    prog = host.open_program(blob=blob, spec=spec)
+    assert prog.kernels == table
+    rng = np.random.default_rng(7)
+    n_cells = int(np.prod(shape))
+    din = [host.DeviceArray(n_cells * dt.itemsize) for dt in prog.in_dtypes]
+    dout = [host.DeviceArray(n_cells * dt.itemsize) for dt in prog.out_dtypes]
+    for d, dt in zip(din, prog.in_dtypes):
+      a = rng.random(shape, dtype=np.float32)
+      d.upload(a.astype(dt))
+      del a
+    pin, pout = [d.ptr for d in din], [d.ptr for d in dout]
+    # (name, depth limit, fixed split)
+    schedules = [(default, limit, None)] + [
+        ('depth %d' % k['depth'], limit, [k['depth']] * (iterate // k['depth'])) for k in fused] + [
+            ('per-stage', -1, None)]
+    launches = {}
+
+    def run(name, depth_limit, split, repeats):
+      prog.set_max_depth(depth_limit)
+      if split:
+        prog.set_split(dims, iterate, split)
+      try:
+        launches[name] = [e['name'] for e, _ in prog.schedule(dims, iterate)]
+        return prog.sweep_timed(pin, pout, dims, iterate, warmup=0, repeats=repeats)
+      finally:
+        if split:
+          prog.set_split(dims, iterate, [])
+        prog.set_max_depth(0)
+
+    # every schedule's results at this size, bit for bit on every output's box, first
+    boxes = []
+    for name in spec['outputs']:
+      lo, hi = specmod.iteration_boxes(spec, iterate)[-1][name]
+      boxes.append(tuple(slice(-lo[d], dims[d] - hi[d]) for d in (1, 0)))
+    reference, same = None, {}
+    for name, depth_limit, split in reversed(schedules):
+      for d in dout:
+        d.zero()
+      run(name, depth_limit, split, 1)
+      got = [np.ascontiguousarray(d.download(shape, dt)[sl])
+             for d, dt, sl in zip(dout, prog.out_dtypes, boxes)]
+      if reference is None:
+        reference = got
+      same[name] = all(np.array_equal(g.view(np.uint8), r.view(np.uint8))
+                       for g, r in zip(got, reference))
+      del got
+    del reference
+    assert launches['per-stage'] == stage_names * iterate, launches['per-stage']
+    assert all(n.startswith(app + '_fused_k') for n in launches[default]), launches[default]
+    for k in fused:
+      assert launches['depth %d' % k['depth']] == [k['name']] * (iterate // k['depth'])
+    assert all(same.values()), '%s: outputs differ from the per-stage outputs: %s' % (app, same)
+    times = {name: [] for name, _, _ in schedules}
+    for r in range(args.warmup + args.sweeps):     # alternating: drift hits all alike
+      for name, depth_limit, split in schedules:
+        t = run(name, depth_limit, split, args.repeats)
+        if r >= args.warmup:
+          times[name].append(t['kernel_us'] / 1e3)
+    updates = specmod.valid_cells(spec, dims, iterate)
+    alg = specmod.algorithmic_bytes_per_update(spec)
+    med = {n: statistics.median(ts) for n, ts in times.items()}
+    lines.append('%s %s x %d, %d timed rounds of %d sweeps each; outputs of all schedules '
+                 'bit-identical on every box' % (app, ' x '.join(map(str, dims)), iterate,
+                                                 args.sweeps, args.repeats))
+    lines.append('  schedule     ms per sweep: median  min .. max      launches  us per launch  '
+                 'us per iteration  Gcell/s  TB/s alg.  against per-stage')
+    record = dict(app=app, dims=list(dims), iterate=iterate, ms=med, schedules={})
+    for name, _, _ in schedules:
+      ts = sorted(times[name])
+      spread = max(ts[-1] - ts[0], max(times['per-stage']) - min(times['per-stage']))
+      verdict = '' if name == 'per-stage' else (
+          'FASTER' if med['per-stage'] - med[name] > spread else
+          'SLOWER' if med[name] - med['per-stage'] > spread else 'NO DIFFERENCE beyond the spread')
+      n = len(launches[name])
+      lines.append('  %-10s %12.3f  %10.3f .. %-10.3f %6d  %13.1f  %16.1f  %7.1f  %9.2f  %s' % (
+          name, med[name], ts[0], ts[-1], n, med[name] * 1e3 / n, med[name] * 1e3 / iterate,
+          updates / (med[name] * 1e-3) / 1e9, alg * updates / (med[name] * 1e-3) / 1e12,
+          '' if name == 'per-stage' else '%.2f x, %s (spread %.3f ms)' % (
+              med['per-stage'] / med[name], verdict, spread)))
+      record['schedules'][name] = dict(ms=med[name], min_ms=ts[0], max_ms=ts[-1], launches=n,
+                                       speedup=med['per-stage'] / med[name], verdict=verdict)
+    lines.append('  %s schedule: %s' % (default, ' '.join(
+        '%d x %s' % (launches[default].count(n), n) for n in sorted(set(launches[default])))))
+    for k in fused:
+      f = static_figures(blob, k['name'])
+      lines.append('  %-22s period %2d, halo %d/%d, %3d columns out; %s' % (
+          k['name'], k['period'], k['halo'][0], k['halo'][1], k['w_out'],
+          '%d VGPRs (estimate %d), %d SGPRs, scratch %d B, spills %d VGPR / %d SGPR, code %d B' % (
+              f['vgpr_count'], k['est_vgprs'], f['sgpr_count'], f['private_segment_fixed_size'],
+              f['vgpr_spill_count'], f['sgpr_spill_count'], code_bytes(blob, k['name']))
+          if f else '(no code object here)'))
+    lines.append('')
+    for d in din + dout:
+      d.free()
+    prog.close()
+    print(json.dumps(record), flush=True)
+  text = '\n'.join(lines) + '\n'
+  print(text)
+  if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, 'w') as f:
+      f.write(text)
+
+
+if __name__ == '__main__':
+  main()

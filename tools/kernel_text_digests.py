@@ -7,7 +7,8 @@ selection must give zero differing lines, the error lines included).
 
 The opt-in switches of generate() (fuse_outputs, lds_planes, lds_fields, lds_ring) are cases
 too (the cases of the first three are printed first and as they were before `lds_ring`
-existed, those with `lds_ring` after them: an older tree's output is a prefix-wise subset), and
+existed, those with `lds_ring` after them, those with `far_lanes` after these: an older
+tree's output is a prefix-wise subset), and
 what is derived from them outside the generator has lines of its own: `host/...`, the sha256
 of the generated Python and C++ host texts per combination of switches, and `file/...`, the
 name of the prebuilt code object per combination build() uses.
@@ -102,6 +103,7 @@ BEFORE_RING = SWITCHES[:3]
 LDS_SAMPLES = [(app, dict(lds_planes=True)) for app in lds3d.APPS] + [
     (app, lds3d_fields.switches(app)) for app in lds3d_fields.APPS]
 RING_SAMPLES = [(app, dict(lds_ring=True)) for app in entry.LDS_RING_APPS]
+FAR_SAMPLES = [(app, dict(far_lanes=True)) for app in entry.FAR_LANES_APPS]
 HOST_PROGRAMS = ('jacobi2d', 'grad2d', 'grad3d', 'star3d', 'acoustic3d', 'deriv3d')
 HOST_CPP_SWITCHES = ('fuse_outputs', 'lds_fields')      # the keywords host_cpp.print_code took
 
@@ -233,6 +235,21 @@ def cases():
     make = lambda t=text: specmod.spec_from_stencil(frontend.loads(t))
     for on in with_ring:
       yield 'inline/%s/%s' % (key, show(on)), make, on
+  # `far_lanes`: alone and with the other four on every sample and program text, and its
+  # samples at the iteration counts that change their depths
+  with_far = [dict(far_lanes=True), dict({n: True for n in SWITCHES}, far_lanes=True)]
+  for path in sorted(glob.glob(os.path.join(SAMPLES, '*.soda')) +
+                     glob.glob(os.path.join(SAMPLES, 'extra', '*.soda'))):
+    app = os.path.basename(path)[:-5]
+    for on in with_far:
+      yield 'switch/%s/%s' % (app, show(on)), (lambda a=app: spec_of(a, None)), on
+  for app, on in FAR_SAMPLES:
+    for iterate in (1, 2, 3, None):
+      yield 'far_iterate/%s/%s' % (app, iterate), (lambda a=app, i=iterate: spec_of(a, i)), on
+  for key, text in inline_texts():
+    make = lambda t=text: specmod.spec_from_stencil(frontend.loads(t))
+    for on in with_far:
+      yield 'inline/%s/%s' % (key, show(on)), make, on
 
 
 def digest(text):
@@ -268,6 +285,13 @@ def host_lines():
                    (entry.LDS_FIELDS_APPS, dict(lds_fields=True)),
                    (entry.LDS_RING_APPS, {}), (entry.LDS_RING_APPS, dict(lds_ring=True))):
     for app in apps:
+      yield 'file/%s/%s %s' % (app, show(on), os.path.basename(entry.blob_path(app, **on)))
+  for app in HOST_PROGRAMS + entry.FAR_LANES_APPS:
+    out = io.StringIO()
+    host_shim.print_code(spec_of(app, None), out, far_lanes=True)
+    yield 'host/shim/%s/far_lanes %s' % (app, digest(out.getvalue()))
+  for on in ({}, dict(far_lanes=True)):
+    for app in entry.FAR_LANES_APPS:
       yield 'file/%s/%s %s' % (app, show(on), os.path.basename(entry.blob_path(app, **on)))
 
 
