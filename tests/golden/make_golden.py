@@ -421,6 +421,75 @@ CASES_3D = [(20, 18, 16), (33, 9, 12)]
 EXTRA = os.path.join(os.path.dirname(HERE), 'samples', 'extra')
 
 
+def write_family(out_dir, manifest_path, apps, cases, kinds=('ramp', 'random'),
+                 refusal_prefix=None, refusals=()):
+  """The loop of the make_<family>_golden.py scripts: every program of `apps`
+  ((app of tests/samples/extra, iteration counts), ...) on every grid of `cases` (a tuple,
+  or a function of the stencil) with every kind of input, through the reference's loops at
+  -O0 and at -O2 -ffp-contract=off, which must agree.  Writes <out_dir>/<key>.<grid>.<kind>.npz
+  and the manifest.  `refusals` names the ways in which the reference does not take a
+  program that end in a manifest row '<refusal_prefix>.<key>' instead of an error here:
+  'raises' (its analysis or host printer raises), 'fed_back' (an output is read by another
+  stage: the emitted loops read the device's array there, main_extra) and 'compile' (the
+  emitted loops do not compile)."""
+  manifest = {}
+
+  def refuse(key, why, said):
+    manifest['%s.%s' % (refusal_prefix, key)] = dict(key=key, reference_cpu_path=why)
+    print(key, said)
+
+  with tempfile.TemporaryDirectory() as wd:
+    for app, iterations in apps:
+      for it in iterations:
+        key = '%s.iter%d' % (app, it)
+        try:
+          st = build_stencil(os.path.join(EXTRA, app + '.soda'), iterate=it)
+          ana, text = analysis_of(st)
+        except Exception as e:      # the reference itself does not take the program
+          if 'raises' not in refusals:
+            raise
+          refuse(key, 'the reference raises %s: %s' % (type(e).__name__, str(e)[:200]),
+                 ': the reference raises %s %s' % (type(e).__name__, e))
+          continue
+        fed_back = [t['name'] for t in ana['stages']
+                    if t['name'] in st.output_names and not t['is_output']]
+        if fed_back and 'fed_back' in refusals:
+          refuse(key, 'reads the device result of output(s) %s' % ', '.join(fed_back),
+                 ': output read by another stage, no self-contained reference answer')
+          continue
+        for dims in (cases(st) if callable(cases) else cases):
+          for kind in kinds:
+            inputs = make_inputs(st, dims, kind, np.random.default_rng(SEED))
+            try:
+              r0 = run_reference(st, text, dims, inputs, '-O0', wd)
+              r2 = run_reference(st, text, dims, inputs, '-O2 -ffp-contract=off', wd)
+            except subprocess.CalledProcessError:
+              if 'compile' not in refusals:
+                raise
+              refuse(key, 'does not compile',
+                     ': the reference\'s emitted CPU loops do not compile')
+              break
+            outs = {n: r0[n] for n in st.output_names}
+            for name in outs:
+              if not np.array_equal(r0[name], r2[name], equal_nan=True):
+                raise SystemExit('O0/O2 disagree: %s %s' % (key, name))
+            fx = '%s.%s.%s.npz' % (key, 'x'.join(map(str, dims)), kind)
+            payload = {'in_' + n: a for n, a in zip(st.input_names, inputs)}
+            payload.update({'out_' + n: a for n, a in outs.items()})
+            os.makedirs(out_dir, exist_ok=True)    # a family without a fixture: no directory
+            np.savez_compressed(os.path.join(out_dir, fx), **payload)
+            manifest[fx] = dict(key=key, dims=list(dims), kind=kind, iterate=it,
+                                sha256={n: hashlib.sha256(a.tobytes()).hexdigest()
+                                        for n, a in outs.items()})
+            print('wrote', fx)
+          else:
+            continue
+          break
+  os.makedirs(os.path.dirname(manifest_path), exist_ok=True)
+  with open(manifest_path, 'w') as f:
+    json.dump(manifest, f, indent=1, sort_keys=True)
+
+
 def main_extra():
   """Fixtures for the hand-written programs of tests/samples/extra (features no
   reference sample uses: let, casts, ~lat, two-argument C calls, one-sided

@@ -11,12 +11,7 @@ at least): the grids here are (41, 19, 18) and (23, 27, 21) as (x, y, z).  itera
 (iso3dfd, one pass over three inputs: 1), ramp and seeded-random inputs.  Writes
 lds3d/*.npz and lds3d_manifest.json.  Only DATA produced by the reference is committed.
 """
-import hashlib
-import json
 import os
-import tempfile
-
-import numpy as np
 
 import make_golden as mg
 
@@ -24,37 +19,6 @@ APPS = (('star3d', (1, 2)), ('iso3dfd', (1,)), ('skewstar3d', (1, 2)))
 CASES = ((41, 19, 18), (23, 27, 21))
 OUT = os.path.join(mg.HERE, 'lds3d')
 
-
-def main():
-  os.makedirs(OUT, exist_ok=True)
-  manifest = {}
-  with tempfile.TemporaryDirectory() as wd:
-    for app, iterations in APPS:
-      path = os.path.join(mg.EXTRA, app + '.soda')
-      for it in iterations:
-        st = mg.build_stencil(path, iterate=it)
-        _, text = mg.analysis_of(st)
-        key = '%s.iter%d' % (app, it)
-        for dims in CASES:
-          for kind in ('ramp', 'random'):
-            inputs = mg.make_inputs(st, dims, kind, np.random.default_rng(mg.SEED))
-            r0 = mg.run_reference(st, text, dims, inputs, '-O0', wd)
-            r2 = mg.run_reference(st, text, dims, inputs, '-O2 -ffp-contract=off', wd)
-            outs = {n: r0[n] for n in st.output_names}
-            for name in outs:
-              if not np.array_equal(r0[name], r2[name], equal_nan=True):
-                raise SystemExit('O0/O2 disagree: %s %s' % (key, name))
-            fx = '%s.%s.%s.npz' % (key, 'x'.join(map(str, dims)), kind)
-            payload = {'in_' + n: a for n, a in zip(st.input_names, inputs)}
-            payload.update({'out_' + n: a for n, a in outs.items()})
-            np.savez_compressed(os.path.join(OUT, fx), **payload)
-            manifest[fx] = dict(key=key, dims=list(dims), kind=kind, iterate=it,
-                                sha256={n: hashlib.sha256(a.tobytes()).hexdigest()
-                                        for n, a in outs.items()})
-            print('wrote', fx)
-  with open(os.path.join(mg.HERE, 'lds3d_manifest.json'), 'w') as f:
-    json.dump(manifest, f, indent=1, sort_keys=True)
-
-
 if __name__ == '__main__':
-  main()
+  mg.write_family(OUT, os.path.join(mg.HERE, 'lds3d_manifest.json'),
+                  APPS, CASES)

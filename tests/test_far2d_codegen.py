@@ -21,7 +21,7 @@ from soda_hip.codegen import (host_shim, kernel, kernel_common, kernel_fields2d,
 from soda_hip.codegen import spec as specmod
 
 from conftest import ROOT, SAMPLES
-from test_lds3d_codegen import HIPCC, READELF, SODAC, spec_of, spec_of_text, without_meta
+from codegen_util import HIPCC, SODAC, resource_figures, spec_of, spec_of_text, without_meta
 
 APPS = ('star2d', 'dstar2d', 'skewfar2d', 'acoustic2d')
 # per sample, per fused depth: (halo lo, halo hi, output columns of a strip, rotation period).
@@ -214,27 +214,17 @@ def test_the_shipped_unit_compiles_inside_its_estimate(app, tmp_path):
   spec = spec_of(app, iterate=entry.BLOB_ITERATE.get(app))
   text, table = kernel.generate(spec, far_lanes=True)
   assert (text, table) == generated(app)
-  out = str(tmp_path / (app + '.hsaco'))
-  kernel.compile_to_code_object(text, out, extra_flags=['-Werror=array-bounds'])
-  notes = subprocess.check_output([READELF, '--notes', out]).decode()
   fused = [k for k in table if k['kind'] == 'fused']
   assert fused
+  found = resource_figures(text, [k['name'] for k in fused], str(tmp_path / (app + '.hsaco')),
+                           extra_flags=['-Werror=array-bounds'])
   for k in fused:
-    block = [b for b in notes.split('- .agpr_count')
-             if '.name:           %s\n' % k['name'] in b or '.name: %s\n' % k['name'] in b]
-    assert len(block) == 1, (k['name'], len(block))
-    figures = {}
-    for line in block[0].splitlines():
-      line = line.strip()
-      for key in ('.private_segment_fixed_size', '.vgpr_spill_count', '.sgpr_spill_count',
-                  '.vgpr_count'):
-        if line.startswith(key + ':'):
-          figures[key] = int(line.split(':', 1)[1])
+    figures = found[k['name']]
     print(k['name'], figures, 'estimate', k['est_vgprs'])
-    assert figures['.private_segment_fixed_size'] == 0, (k['name'], figures)
-    assert figures['.vgpr_spill_count'] == 0, (k['name'], figures)
-    assert figures['.sgpr_spill_count'] == 0, (k['name'], figures)
-    assert 0 < figures['.vgpr_count'] <= k['est_vgprs'], (
+    assert figures['private_segment_fixed_size'] == 0, (k['name'], figures)
+    assert figures['vgpr_spill_count'] == 0, (k['name'], figures)
+    assert figures['sgpr_spill_count'] == 0, (k['name'], figures)
+    assert 0 < figures['vgpr_count'] <= k['est_vgprs'], (
         k['name'], figures, k['est_vgprs'], 're-fit the weights of kernel_stream2d.far_vgprs')
 
 

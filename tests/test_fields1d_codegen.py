@@ -15,10 +15,10 @@ import subprocess
 import numpy as np
 import pytest
 
-from soda_hip import frontend
 from soda_hip.codegen import kernel, kernel_fields1d, kernel_stream1d
 from soda_hip.codegen import spec as specmod
 
+from codegen_util import HIPCC, READELF, resource_figures, spec_of, spec_of_text
 from conftest import ROOT, SAMPLES
 import test_schedule as ts
 import test_schedule_fields as tsf
@@ -33,22 +33,12 @@ DEPTHS = {'wave1d': [1, 2, 4, 8], 'skewpair1d': [1, 2, 4], 'fdtd1d': [1, 2, 4, 8
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 with open(os.path.join(GOLDEN, 'fields1d_manifest.json')) as _f:
   MANIFEST = json.load(_f)
-HIPCC = s1d.HIPCC
-READELF = s1d.READELF
 LANES = 64
 
 
 def sample_path(app):
   path = os.path.join(SAMPLES, app + '.soda')
   return path if os.path.exists(path) else os.path.join(SAMPLES, 'extra', app + '.soda')
-
-
-def spec_of(app, **kw):
-  return specmod.spec_from_stencil(frontend.load(sample_path(app), **kw))
-
-
-def spec_of_text(text):
-  return specmod.spec_from_stencil(frontend.loads(text))
 
 
 def retyped(app, dsl_type, was='float'):
@@ -455,25 +445,12 @@ def test_kernels_compile_for_gfx950_within_128_registers(which, tmp_path):
   SGPR, at most 128 VGPRs (four wavefronts per SIMD)."""
   spec = PROGRAMS[which]()
   text, table = kernel.generate(spec)
-  out = str(tmp_path / (which + '.hsaco'))
-  kernel.compile_to_code_object(text, out)
-  notes = subprocess.check_output([READELF, '--notes', out]).decode()
   fused = [k['name'] for k in table if k['kind'] == 'fused']
   assert len(fused) == len(DEPTHS[which.split('_')[0]])
-  blocks = notes.split('- .agpr_count')
-  for kname in fused:
-    block = [b for b in blocks if '.name:           %s\n' % kname in b or
-             '.name: %s\n' % kname in b]
-    assert len(block) == 1, (kname, len(block))
-    figures = {}
-    for line in block[0].splitlines():
-      line = line.strip()
-      for key in ('.private_segment_fixed_size', '.vgpr_spill_count', '.sgpr_spill_count',
-                  '.vgpr_count'):
-        if line.startswith(key + ':'):
-          figures[key] = int(line.split(':', 1)[1])
+  found = resource_figures(text, fused, str(tmp_path / (which + '.hsaco')))
+  for kname, figures in found.items():
     print(kname, figures)
-    assert figures['.private_segment_fixed_size'] == 0, (kname, figures)
-    assert figures['.vgpr_spill_count'] == 0, (kname, figures)
-    assert figures['.sgpr_spill_count'] == 0, (kname, figures)
-    assert 0 < figures['.vgpr_count'] <= 128, (kname, figures)
+    assert figures['private_segment_fixed_size'] == 0, (kname, figures)
+    assert figures['vgpr_spill_count'] == 0, (kname, figures)
+    assert figures['sgpr_spill_count'] == 0, (kname, figures)
+    assert 0 < figures['vgpr_count'] <= 128, (kname, figures)

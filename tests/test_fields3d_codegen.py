@@ -6,7 +6,6 @@ the launch planner packs each output's own box into the launch arguments."""
 import json
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ from soda_hip.codegen import kernel, kernel_fields3d, kernel_stream2d, kernel_st
 from soda_hip.codegen import spec as specmod
 
 import test_schedule as ts
+from codegen_util import HIPCC, READELF, resource_figures, spec_of, spec_of_text
 from conftest import ROOT, SAMPLES
 from test_schedule import probe      # noqa: F401  (the planner probe, built once)
 
@@ -23,17 +23,6 @@ APPS = ('wave3d', 'maxwell3d')
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 with open(os.path.join(GOLDEN, 'fields3d_manifest.json')) as _f:
   MANIFEST = json.load(_f)
-HIPCC = os.environ.get('HIPCC') or '/opt/rocm/bin/hipcc'
-READELF = '/opt/rocm/lib/llvm/bin/llvm-readelf'
-
-
-def spec_of(app, **kw):
-  return specmod.spec_from_stencil(frontend.load(os.path.join(SAMPLES, 'extra', app + '.soda'),
-                                                 **kw))
-
-
-def spec_of_text(text):
-  return specmod.spec_from_stencil(frontend.loads(text))
 
 
 @pytest.mark.parametrize('app', APPS)
@@ -98,27 +87,14 @@ def test_kernels_compile_for_gfx950_without_scratch(app, tmp_path):
   """Every fused entry: no private segment (scratch) and no spill counts, neither of
   VGPRs nor of SGPRs."""
   text, table = kernel.generate(spec_of(app))
-  out = str(tmp_path / (app + '.hsaco'))
-  kernel.compile_to_code_object(text, out)
-  notes = subprocess.check_output([READELF, '--notes', out]).decode()
   fused = [k['name'] for k in table if k['kind'] == 'fused']
   assert len(fused) == 2
-  blocks = notes.split('- .agpr_count')
-  for kname in fused:
-    block = [b for b in blocks if '.name:           %s\n' % kname in b or
-             '.name: %s\n' % kname in b]
-    assert len(block) == 1, (kname, len(block))
-    figures = {}
-    for line in block[0].splitlines():
-      line = line.strip()
-      for key in ('.private_segment_fixed_size', '.vgpr_spill_count', '.sgpr_spill_count',
-                  '.vgpr_count'):
-        if line.startswith(key + ':'):
-          figures[key] = int(line.split(':', 1)[1])
-    assert figures['.private_segment_fixed_size'] == 0, (kname, figures)
-    assert figures['.vgpr_spill_count'] == 0, (kname, figures)
-    assert figures['.sgpr_spill_count'] == 0, (kname, figures)
-    assert 0 < figures['.vgpr_count'] <= 256, (kname, figures)
+  found = resource_figures(text, fused, str(tmp_path / (app + '.hsaco')))
+  for kname, figures in found.items():
+    assert figures['private_segment_fixed_size'] == 0, (kname, figures)
+    assert figures['vgpr_spill_count'] == 0, (kname, figures)
+    assert figures['sgpr_spill_count'] == 0, (kname, figures)
+    assert 0 < figures['vgpr_count'] <= 256, (kname, figures)
 
 
 _HEAD = 'kernel: %s\nburst width: 512\nunroll factor: 1\niterate: 4\n'

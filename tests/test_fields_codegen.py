@@ -6,7 +6,6 @@ that the per-output extras a launch carries are the boxes' own differences."""
 import json
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,23 +14,13 @@ from soda_hip import frontend
 from soda_hip.codegen import kernel, kernel_fields2d, kernel_stream2d
 from soda_hip.codegen import spec as specmod
 
+from codegen_util import HIPCC, READELF, resource_figures, spec_of, spec_of_text
 from conftest import ROOT, SAMPLES
 
 APPS = ('wave2d', 'fdtd2d', 'skewpair2d', 'mixpair2d')
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 with open(os.path.join(GOLDEN, 'fields_manifest.json')) as _f:
   MANIFEST = json.load(_f)
-HIPCC = os.environ.get('HIPCC') or '/opt/rocm/bin/hipcc'
-READELF = '/opt/rocm/lib/llvm/bin/llvm-readelf'
-
-
-def spec_of(app, **kw):
-  return specmod.spec_from_stencil(frontend.load(os.path.join(SAMPLES, 'extra', app + '.soda'),
-                                                 **kw))
-
-
-def spec_of_text(text):
-  return specmod.spec_from_stencil(frontend.loads(text))
 
 
 @pytest.mark.parametrize('app', APPS)
@@ -64,27 +53,14 @@ def test_kernels_compile_for_gfx950_without_scratch(app, tmp_path):
   """Every fused entry: no private segment (scratch) and no spill counts, neither of
   VGPRs nor of SGPRs (the allocator parks those in VGPR lanes, inside the row loop)."""
   text, table = kernel.generate(spec_of(app))
-  out = str(tmp_path / (app + '.hsaco'))
-  kernel.compile_to_code_object(text, out)
-  notes = subprocess.check_output([READELF, '--notes', out]).decode()
   fused = [k['name'] for k in table if k['kind'] == 'fused']
   assert fused
-  blocks = notes.split('- .agpr_count')
-  for kname in fused:
-    block = [b for b in blocks if '.name:           %s\n' % kname in b or
-             '.name: %s\n' % kname in b]
-    assert len(block) == 1, (kname, len(block))
-    figures = {}
-    for line in block[0].splitlines():
-      line = line.strip()
-      for key in ('.private_segment_fixed_size', '.vgpr_spill_count', '.sgpr_spill_count',
-                  '.vgpr_count'):
-        if line.startswith(key + ':'):
-          figures[key] = int(line.split(':', 1)[1])
-    assert figures['.private_segment_fixed_size'] == 0, (kname, figures)
-    assert figures['.vgpr_spill_count'] == 0, (kname, figures)
-    assert figures['.sgpr_spill_count'] == 0, (kname, figures)
-    assert 0 < figures['.vgpr_count'] <= 256, (kname, figures)
+  found = resource_figures(text, fused, str(tmp_path / (app + '.hsaco')))
+  for kname, figures in found.items():
+    assert figures['private_segment_fixed_size'] == 0, (kname, figures)
+    assert figures['vgpr_spill_count'] == 0, (kname, figures)
+    assert figures['sgpr_spill_count'] == 0, (kname, figures)
+    assert 0 < figures['vgpr_count'] <= 256, (kname, figures)
 
 
 FIXTURES = sorted(k for k in MANIFEST if k.endswith('.npz'))

@@ -4,125 +4,41 @@ limit of 1: the reference's fixtures array for array, shapes taken from the entr
 constants - every output on its own box against the oracle, the whole arrays against the
 per-stage run -, the ping-pong of three fields over several iterations, the sweep's memory
 contract in guarded arenas, full-width operands, and the run-time compile with the switch.
-Every comparison is of bytes."""
-import json
-import os
+Every comparison is of bytes (tests/switch_form_gpu.py)."""
+import functools
 
-import numpy as np
 import pytest
 
-from soda_hip.codegen import kernel
-from soda_hip.codegen import spec as specmod
-from soda_hip.runtime import host
-
-import gpu_util
-from conftest import ROOT
-from test_gpu_lds3d import SHORTEST_CHUNK
-from test_gpu_memory_contract import box_of, hold
+import switch_form_gpu as harness
 
 pytestmark = pytest.mark.gpu
 
 APPS = ('acoustic3d', 'skewwave3d', 'deriv3d')
-GOLDEN = os.path.join(ROOT, 'tests', 'golden')
-with open(os.path.join(GOLDEN, 'lds3d_fields_manifest.json')) as _f:
-  MANIFEST = json.load(_f)
-
-_CACHE = {}
 
 
-def opened(app):
-  """(program from the prebuilt code object generated with lds_fields=True, oracle)"""
-  if app not in _CACHE:
-    spec = gpu_util.load_spec(app)
-    path = os.path.join(gpu_util.BLOBS, app + '.ldsf.hsaco')
-    assert os.path.exists(path), '%s missing: run __graft_entry__.build()' % path
-    prog = host.open_program(blob=path, spec=spec)
-    _CACHE[app] = (prog, gpu_util.make_oracle(spec))
-  return _CACHE[app]
+def _check(fused, spec):
+  assert fused[0]['fields'] == len(spec['outputs'])
 
 
-def entry_of(prog):
-  (k,) = [k for k in prog.kernels if k['kind'] == 'fused']
-  assert k['name'] == prog.spec['app_name'] + '_fused_k1lf' and k['depth'] == 1
-  assert k['fields'] == len(prog.spec['outputs'])
-  return k
+FORM = harness.Form(
+    keyword='lds_fields', family='lds3d_fields',
+    fixtures=lambda app: 4 if app == 'deriv3d' else 8,
+    kernels=lambda spec: [(spec['app_name'] + '_fused_k1lf', 1)],
+    limit=lambda spec: 1, margins=harness.hull_margins, check=_check)
 
 
-def margins(spec, iterate):
-  """Cells the intersection of the outputs' boxes after `iterate` iterations is shorter than
-  the array: the hull's lo + hi margin, (x, y, z)."""
-  lo, hi = specmod.iteration_margins(spec, iterate)[-1]
-  return [a + b for a, b in zip(lo, hi)]
+opened = functools.partial(harness.opened, FORM)
+check_shape = functools.partial(harness.check_shape, FORM)
 
 
 def shapes_of(prog, iterate):
-  """(z, y, x) from the entry's own constants: an intersection box of one cell each way (the
-  wider outputs then live almost entirely outside the launch's box); one tile plus one
-  column and one row with fewer planes than fill_rows + 1; two of the shortest chunks less
-  one plane, a few cells wide; a ragged grid of 2 x 3 tiles plus odd remainders, 29 planes."""
-  k = entry_of(prog)
-  mx, my, mz = margins(prog.spec, iterate)
-  tx, ty = k['tile'][:2]
-  assert k['fill_rows'] >= 2
-  return [(mz + 1, my + 1, mx + 1),
-          (mz + k['fill_rows'] - 1, ty + 1 + my, tx + 1 + mx),
-          (mz + 2 * SHORTEST_CHUNK - 1, my + 3, mx + 5),
-          (mz + 29, 3 * ty + 5 + my, 2 * tx + 37 + mx)]
-
-
-def fused_and_staged(prog, inputs, iterate):
-  """The arrays of the schedule under depth limit 1 (every launch the LDS-plane kernel) and
-  the per-stage run's."""
-  dims = tuple(reversed(inputs[0].shape))
-  name = prog.spec['app_name'] + '_fused_k1lf'
-  stages = [k['name'] for k in prog.kernels if k['kind'] == 'stage']
-  try:
-    prog.set_max_depth(1)
-    assert [k['name'] for k, _ in prog.schedule(dims, iterate)] == [name] * iterate
-    got = prog.run_numpy(inputs, iterate=iterate)
-    prog.set_max_depth(-1)
-    assert [k['name'] for k, _ in prog.schedule(dims, iterate)] == stages * iterate
-    staged = prog.run_numpy(inputs, iterate=iterate)
-  finally:
-    prog.set_max_depth(0)
-  return got, staged
+  (k,) = harness.fused_of(FORM, prog)
+  return harness.shapes_of(FORM, k, prog.spec, iterate)
 
 
 @pytest.mark.parametrize('app', APPS)
 def test_fixtures(app):
-  """The whole arrays equal the reference's: each output on its box, zero outside; the same
-  arrays per stage."""
-  prog, _ = opened(app)
-  spec = prog.spec
-  n = 0
-  for fx, meta in sorted(MANIFEST.items()):
-    if not meta['key'].startswith(app + '.'):
-      continue
-    data = np.load(os.path.join(GOLDEN, 'lds3d_fields', fx))
-    inputs = [data['in_' + t['name']] for t in spec['inputs']]
-    got, staged = fused_and_staged(prog, inputs, meta['iterate'])
-    for name, g, s in zip(spec['outputs'], got, staged):
-      want = data['out_' + name]
-      assert np.array_equal(g.view(np.uint8), want.view(np.uint8)), (fx, name)
-      assert np.array_equal(s.view(np.uint8), want.view(np.uint8)), (fx, name, 'per stage')
-    n += 1
-  assert n == (4 if app == 'deriv3d' else 8)
-
-
-def check_shape(prog, orc, shape, iterate):
-  spec = prog.spec
-  dims = tuple(reversed(shape))
-  inputs = gpu_util.random_inputs(spec, shape, seed=gpu_util.SEED + sum(shape))
-  want = orc.run(inputs, iterate=iterate)
-  got, staged = fused_and_staged(prog, inputs, iterate)
-  for name, g, s in zip(spec['outputs'], got, staged):
-    lo, hi = box_of(spec, name, dims, iterate)
-    sl = tuple(slice(a, b) for a, b in zip(reversed(lo), reversed(hi)))
-    assert g[sl].size > 0, (name, shape, iterate)
-    assert np.array_equal(np.ascontiguousarray(g[sl]).view(np.uint8),
-                          np.ascontiguousarray(want[name][sl]).view(np.uint8)), \
-        (name, shape, iterate)
-    assert np.array_equal(g.view(np.uint8), s.view(np.uint8)), (name, shape, iterate)
+  harness.fixtures(FORM, app)
 
 
 @pytest.mark.parametrize('app', APPS)
@@ -146,62 +62,18 @@ def test_iterated(app, iterate):
 
 @pytest.mark.parametrize('app,iterate', [('acoustic3d', 3), ('skewwave3d', 2), ('deriv3d', 1)])
 def test_memory_contract(app, iterate):
-  """gpu_util.run_guarded on the smallest and on the ragged shape, from the pool allocator's
-  placement and from multiples of 64 and 16 bytes: every output's box equals the oracle,
-  guards intact, inputs unchanged."""
-  prog, orc = opened(app)
-  shapes = shapes_of(prog, iterate)
-  prog.set_max_depth(1)
-  try:
-    for shape, modes in ((shapes[0], ('pool', 'aligned')), (shapes[-1], ('pool', 'sixteen'))):
-      for mode in modes:
-        launched = hold(prog, orc, shape, iterate, mode, 'stream', 1)
-        assert [k['name'] for k in launched] == [app + '_fused_k1lf'] * iterate
-  finally:
-    prog.set_max_depth(0)
+  """The smallest and the ragged shape, from the pool allocator's placement and from
+  multiples of 64 and 16 bytes."""
+  harness.memory_contract(FORM, app, iterate, ((0, ('pool', 'aligned')),
+                                               (-1, ('pool', 'sixteen'))))
 
 
 @pytest.mark.parametrize('app,iterate', [('acoustic3d', 2), ('skewwave3d', 2), ('deriv3d', 1)])
 def test_full_width_operands(app, iterate):
-  """Mixed signs and exponents over the element's whole mantissa (gpu_util.wide_inputs at
-  the default span), in float (acoustic3d, deriv3d) and in double (skewwave3d).  The
-  oracle's values on every output's box are finite: no NaN payload enters the byte
-  comparison."""
-  prog, orc = opened(app)
-  spec = prog.spec
-  assert spec['inputs'][0]['c_type'] == ('double' if app == 'skewwave3d' else 'float')
-  k = entry_of(prog)
-  mx, my, mz = margins(spec, iterate)
-  shape = (mz + 11, k['tile'][1] + 9 + my, k['tile'][0] + 35 + mx)
-  inputs = gpu_util.wide_inputs(spec, shape)
-  want = orc.run(inputs, iterate=iterate)
-  for name in spec['outputs']:
-    lo, hi = box_of(spec, name, tuple(reversed(shape)), iterate)
-    sl = tuple(slice(a, b) for a, b in zip(reversed(lo), reversed(hi)))
-    assert want[name][sl].size > 0 and np.isfinite(want[name][sl]).all(), name
-  prog.set_max_depth(1)
-  try:
-    launched = hold(prog, orc, shape, iterate, 'pool', 'stream', 1, inputs=inputs)
-    assert [k['name'] for k in launched] == [app + '_fused_k1lf'] * iterate
-  finally:
-    prog.set_max_depth(0)
+  """In float (acoustic3d, deriv3d) and in double (skewwave3d)."""
+  harness.full_width_operands(FORM, app, iterate,
+                              'double' if app == 'skewwave3d' else 'float')
 
 
 def test_run_time_compile_with_the_switch():
-  """host.open_program(spec=..., lds_fields=True): the offline build's table, bit-exact on
-  the ragged shape; without the switch the per-stage kernels only."""
-  spec = gpu_util.load_spec('skewwave3d')
-  prog = host.open_program(spec=spec, lds_fields=True)
-  try:
-    assert prog.kernels == kernel.generate(spec, lds_fields=True)[1]
-    assert prog.kernels == opened('skewwave3d')[0].kernels
-    check_shape(prog, opened('skewwave3d')[1], shapes_of(prog, 2)[-1], 2)
-  finally:
-    prog.close()
-    prog.blob.unload()
-  plain = host.open_program(spec=spec)
-  try:
-    assert [k['kind'] for k in plain.kernels] == ['stage', 'stage']
-  finally:
-    plain.close()
-    plain.blob.unload()
+  harness.run_time_compile(FORM, 'skewwave3d', 2, ['stage', 'stage'])

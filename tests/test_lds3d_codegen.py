@@ -14,12 +14,13 @@ import sys
 import numpy as np
 import pytest
 
-from soda_hip import frontend
 from soda_hip.codegen import (kernel, kernel_common, kernel_stage, kernel_stream2d,
                               kernel_stream3d_lds)
 from soda_hip.codegen import spec as specmod
 
 import test_schedule as ts
+from codegen_util import (HIPCC, READELF, SODAC, notes_of, resource_figures, spec_of,
+                          spec_of_text, without_meta)
 from conftest import ROOT, SAMPLES
 from test_schedule import probe      # noqa: F401  (the planner probe, built once)
 
@@ -30,29 +31,6 @@ with open(os.path.join(GOLDEN, 'lds3d_manifest.json')) as _f:
   MANIFEST = json.load(_f)
 with open(os.path.join(GOLDEN, 'random_programs.json')) as _f:
   RANDOM = json.load(_f)
-HIPCC = os.environ.get('HIPCC') or '/opt/rocm/bin/hipcc'
-READELF = '/opt/rocm/lib/llvm/bin/llvm-readelf'
-SODAC = os.path.join(ROOT, 'soda-compiler_amd', 'sodac')
-
-
-def spec_of(app, **kw):
-  path = os.path.join(SAMPLES, app + '.soda')
-  if not os.path.exists(path):
-    path = os.path.join(SAMPLES, 'extra', app + '.soda')
-  return specmod.spec_from_stencil(frontend.load(path, **kw))
-
-
-def spec_of_text(text):
-  return specmod.spec_from_stencil(frontend.loads(text))
-
-
-def notes_of(text):
-  return [l for l in text.splitlines() if l.startswith('// ') and 'not fused' in l]
-
-
-def without_meta(text):
-  return text[:text.index('const char soda_hip_meta[]')]
-
 
 def lds_note(text):
   return kernel_common.read_meta_from_source(text).get('lds_planes')
@@ -151,25 +129,14 @@ def test_kernels_compile_for_gfx950_without_scratch_or_spills(app, tmp_path):
   parked in VGPR lanes, the static LDS of the entry; array subscripts in bounds at compile
   time."""
   text, table = kernel.generate(spec_of(app), lds_planes=True)
-  out = str(tmp_path / (app + '.hsaco'))
-  kernel.compile_to_code_object(text, out, extra_flags=['-Werror=array-bounds'])
-  notes = subprocess.check_output([READELF, '--notes', out]).decode()
   kname = table[-1]['name']
-  block = [b for b in notes.split('- .agpr_count')
-           if '.name:           %s\n' % kname in b or '.name: %s\n' % kname in b]
-  assert len(block) == 1, (kname, len(block))
-  figures = {}
-  for line in block[0].splitlines():
-    line = line.strip()
-    for key in ('.private_segment_fixed_size', '.vgpr_spill_count', '.sgpr_spill_count',
-                '.vgpr_count', '.group_segment_fixed_size'):
-      if line.startswith(key + ':'):
-        figures[key] = int(line.split(':', 1)[1])
-  assert figures['.private_segment_fixed_size'] == 0, (kname, figures)
-  assert figures['.vgpr_spill_count'] == 0, (kname, figures)
-  assert figures['.sgpr_spill_count'] == 0, (kname, figures)
-  assert 0 < figures['.vgpr_count'] <= 256, (kname, figures)
-  assert figures['.group_segment_fixed_size'] == table[-1]['lds_bytes'], (kname, figures)
+  figures = resource_figures(text, [kname], str(tmp_path / (app + '.hsaco')),
+                             extra_flags=['-Werror=array-bounds'])[kname]
+  assert figures['private_segment_fixed_size'] == 0, (kname, figures)
+  assert figures['vgpr_spill_count'] == 0, (kname, figures)
+  assert figures['sgpr_spill_count'] == 0, (kname, figures)
+  assert 0 < figures['vgpr_count'] <= 256, (kname, figures)
+  assert figures['group_segment_fixed_size'] == table[-1]['lds_bytes'], (kname, figures)
 
 
 # ---- refusals --------------------------------------------------------------------------------

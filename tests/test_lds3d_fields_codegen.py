@@ -22,8 +22,9 @@ from soda_hip.codegen import spec as specmod
 
 import test_schedule_fields as tsf
 from conftest import ROOT, SAMPLES
-from test_lds3d_codegen import (HIPCC, RANDOM, RANDOM_3D, READELF, SODAC, lds_note, notes_of,
-                                spec_of, spec_of_text, without_meta)
+from codegen_util import (HIPCC, READELF, SODAC, notes_of, resource_figures, spec_of,
+                          spec_of_text, without_meta)
+from test_lds3d_codegen import RANDOM, RANDOM_3D, lds_note
 from test_schedule_fields import probes      # noqa: F401  (the planner probes, built once)
 
 APPS = ('acoustic3d', 'skewwave3d', 'deriv3d')
@@ -167,25 +168,14 @@ def test_kernels_compile_for_gfx950_without_scratch_or_spills(app, tmp_path):
   parked in VGPR lanes, the static LDS of the entry; array subscripts in bounds at compile
   time."""
   text, table = kernel.generate(spec_of(app), **switches(app))
-  out = str(tmp_path / (app + '.hsaco'))
-  kernel.compile_to_code_object(text, out, extra_flags=['-Werror=array-bounds'])
-  notes = subprocess.check_output([READELF, '--notes', out]).decode()
   kname = table[-1]['name']
-  block = [b for b in notes.split('- .agpr_count')
-           if '.name:           %s\n' % kname in b or '.name: %s\n' % kname in b]
-  assert len(block) == 1, (kname, len(block))
-  figures = {}
-  for line in block[0].splitlines():
-    line = line.strip()
-    for key in ('.private_segment_fixed_size', '.vgpr_spill_count', '.sgpr_spill_count',
-                '.vgpr_count', '.group_segment_fixed_size'):
-      if line.startswith(key + ':'):
-        figures[key] = int(line.split(':', 1)[1])
-  assert figures['.private_segment_fixed_size'] == 0, (kname, figures)
-  assert figures['.vgpr_spill_count'] == 0, (kname, figures)
-  assert figures['.sgpr_spill_count'] == 0, (kname, figures)
-  assert 0 < figures['.vgpr_count'] <= 256, (kname, figures)
-  assert figures['.group_segment_fixed_size'] == table[-1]['lds_bytes'], (kname, figures)
+  figures = resource_figures(text, [kname], str(tmp_path / (app + '.hsaco')),
+                             extra_flags=['-Werror=array-bounds'])[kname]
+  assert figures['private_segment_fixed_size'] == 0, (kname, figures)
+  assert figures['vgpr_spill_count'] == 0, (kname, figures)
+  assert figures['sgpr_spill_count'] == 0, (kname, figures)
+  assert 0 < figures['vgpr_count'] <= 256, (kname, figures)
+  assert figures['group_segment_fixed_size'] == table[-1]['lds_bytes'], (kname, figures)
 
 
 # ---- refusals --------------------------------------------------------------------------------

@@ -20,8 +20,9 @@ from soda_hip.codegen import (host_shim, kernel, kernel_common, kernel_stage,
 from soda_hip.codegen import spec as specmod
 
 from conftest import ROOT, SAMPLES
-from test_lds3d_codegen import (HIPCC, READELF, SODAC, lds_note, notes_of, spec_of,
-                                without_meta)
+from codegen_util import (HIPCC, READELF, SODAC, notes_of, resource_figures, spec_of,
+                          without_meta)
+from test_lds3d_codegen import lds_note
 from test_lds3d_fields_codegen import fields_note
 
 APPS = ('cross3d', 'skewcross3d', 'coupled3d')
@@ -296,25 +297,14 @@ def test_kernels_compile_for_gfx950_without_scratch_or_spills(app, tmp_path):
   parked in VGPR lanes, the static LDS of the entry; array subscripts in bounds at compile
   time."""
   text, table = generated(app)
-  out = str(tmp_path / (app + '.hsaco'))
-  kernel.compile_to_code_object(text, out, extra_flags=['-Werror=array-bounds'])
-  notes = subprocess.check_output([READELF, '--notes', out]).decode()
   kname = table[-1]['name']
-  block = [b for b in notes.split('- .agpr_count')
-           if '.name:           %s\n' % kname in b or '.name: %s\n' % kname in b]
-  assert len(block) == 1, (kname, len(block))
-  figures = {}
-  for line in block[0].splitlines():
-    line = line.strip()
-    for key in ('.private_segment_fixed_size', '.vgpr_spill_count', '.sgpr_spill_count',
-                '.vgpr_count', '.group_segment_fixed_size'):
-      if line.startswith(key + ':'):
-        figures[key] = int(line.split(':', 1)[1])
-  assert figures['.private_segment_fixed_size'] == 0, (kname, figures)
-  assert figures['.vgpr_spill_count'] == 0, (kname, figures)
-  assert figures['.sgpr_spill_count'] == 0, (kname, figures)
-  assert 0 < figures['.vgpr_count'] <= 256, (kname, figures)
-  assert figures['.group_segment_fixed_size'] == table[-1]['lds_bytes'], (kname, figures)
+  figures = resource_figures(text, [kname], str(tmp_path / (app + '.hsaco')),
+                             extra_flags=['-Werror=array-bounds'])[kname]
+  assert figures['private_segment_fixed_size'] == 0, (kname, figures)
+  assert figures['vgpr_spill_count'] == 0, (kname, figures)
+  assert figures['sgpr_spill_count'] == 0, (kname, figures)
+  assert 0 < figures['vgpr_count'] <= 256, (kname, figures)
+  assert figures['group_segment_fixed_size'] == table[-1]['lds_bytes'], (kname, figures)
 
 
 # ---- the switch is inert elsewhere ------------------------------------------------------------

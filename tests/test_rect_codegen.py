@@ -18,28 +18,14 @@ from soda_hip.codegen import (kernel, kernel_fields2d, kernel_fields3d, kernel_s
                               kernel_stream2d)
 from soda_hip.codegen import spec as specmod
 
+from codegen_util import (HIPCC, READELF, SODAC, notes_of, resource_figures, spec_of,
+                          spec_of_text)
 from conftest import ROOT, SAMPLES
 from test_schedule_fields import extras_of, header, pad4, parse, probes  # noqa: F401
 
 APPS = ('grad2d', 'blend2d', 'grad3d', 'mix3d')
 ALL = APPS + ('outchain',)
 GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'rect')
-HIPCC = os.environ.get('HIPCC') or '/opt/rocm/bin/hipcc'
-READELF = '/opt/rocm/lib/llvm/bin/llvm-readelf'
-SODAC = os.path.join(ROOT, 'soda-compiler_amd', 'sodac')
-
-
-def spec_of(app):
-  return specmod.spec_from_stencil(frontend.load(os.path.join(SAMPLES, 'extra', app + '.soda')))
-
-
-def spec_of_text(text):
-  return specmod.spec_from_stencil(frontend.loads(text))
-
-
-def notes_of(text):
-  return [l for l in text.splitlines() if l.startswith('// ') and 'not fused' in l]
-
 
 @pytest.mark.parametrize('app', ALL)
 def test_a_plain_generate_has_stage_kernels_only(app):
@@ -294,24 +280,13 @@ def test_kernels_compile_for_gfx950_without_scratch_or_spills(app, tmp_path):
   """From the compiler's resource report: no private segment, no spilled VGPRs, no SGPRs
   parked in VGPR lanes; array subscripts in bounds at compile time."""
   text, table = kernel.generate(spec_of(app), fuse_outputs=True)
-  out = str(tmp_path / (app + '.hsaco'))
-  kernel.compile_to_code_object(text, out, extra_flags=['-Werror=array-bounds'])
-  notes = subprocess.check_output([READELF, '--notes', out]).decode()
   kname = table[-1]['name']
-  block = [b for b in notes.split('- .agpr_count')
-           if '.name:           %s\n' % kname in b or '.name: %s\n' % kname in b]
-  assert len(block) == 1, (kname, len(block))
-  figures = {}
-  for line in block[0].splitlines():
-    line = line.strip()
-    for key in ('.private_segment_fixed_size', '.vgpr_spill_count', '.sgpr_spill_count',
-                '.vgpr_count'):
-      if line.startswith(key + ':'):
-        figures[key] = int(line.split(':', 1)[1])
-  assert figures['.private_segment_fixed_size'] == 0, (kname, figures)
-  assert figures['.vgpr_spill_count'] == 0, (kname, figures)
-  assert figures['.sgpr_spill_count'] == 0, (kname, figures)
-  assert 0 < figures['.vgpr_count'] <= 256, (kname, figures)
+  figures = resource_figures(text, [kname], str(tmp_path / (app + '.hsaco')),
+                             extra_flags=['-Werror=array-bounds'])[kname]
+  assert figures['private_segment_fixed_size'] == 0, (kname, figures)
+  assert figures['vgpr_spill_count'] == 0, (kname, figures)
+  assert figures['sgpr_spill_count'] == 0, (kname, figures)
+  assert 0 < figures['vgpr_count'] <= 256, (kname, figures)
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='needs hipcc')

@@ -8,7 +8,6 @@ import hashlib
 import json
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,6 +16,7 @@ from soda_hip import frontend
 from soda_hip.codegen import kernel, kernel_stream1d
 from soda_hip.codegen import spec as specmod
 
+from codegen_util import HIPCC, READELF, resource_figures, spec_of, spec_of_text
 from conftest import ROOT, SAMPLES
 import test_schedule as ts
 from test_schedule import probe      # noqa: F401 - the planner probe, built once per module
@@ -26,23 +26,12 @@ DEPTHS = {'smooth1d': {1, 2, 4, 8, 12}, 'fir1d': {1, 2, 4, 8}}
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 with open(os.path.join(GOLDEN, 'stream1d_manifest.json')) as _f:
   MANIFEST = json.load(_f)
-HIPCC = os.environ.get('HIPCC') or '/opt/rocm/bin/hipcc'
-READELF = '/opt/rocm/lib/llvm/bin/llvm-readelf'
 LANES = 64
 
 
 def sample_text(app):
   with open(os.path.join(SAMPLES, 'extra', app + '.soda')) as f:
     return f.read()
-
-
-def spec_of(app, **kw):
-  return specmod.spec_from_stencil(frontend.load(os.path.join(SAMPLES, 'extra', app + '.soda'),
-                                                 **kw))
-
-
-def spec_of_text(text):
-  return specmod.spec_from_stencil(frontend.loads(text))
 
 
 def retyped(app, dsl_type):
@@ -140,29 +129,16 @@ def test_kernels_compile_for_gfx950_within_128_registers(which, tmp_path):
   VGPRs (four wavefronts per SIMD)."""
   spec = PROGRAMS[which]()
   text, table = kernel.generate(spec)
-  out = str(tmp_path / (which + '.hsaco'))
-  kernel.compile_to_code_object(text, out)
-  notes = subprocess.check_output([READELF, '--notes', out]).decode()
   fused = [k['name'] for k in table if k['kind'] == 'fused']
   assert len(fused) == (4 if which == 'fir1d' else 5)
   elem = specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
   assert all(k['cols'] == 16 // elem for k in table if k['kind'] == 'fused')
-  blocks = notes.split('- .agpr_count')
-  for kname in fused:
-    block = [b for b in blocks if '.name:           %s\n' % kname in b or
-             '.name: %s\n' % kname in b]
-    assert len(block) == 1, (kname, len(block))
-    figures = {}
-    for line in block[0].splitlines():
-      line = line.strip()
-      for key in ('.private_segment_fixed_size', '.vgpr_spill_count', '.sgpr_spill_count',
-                  '.vgpr_count'):
-        if line.startswith(key + ':'):
-          figures[key] = int(line.split(':', 1)[1])
-    assert figures['.private_segment_fixed_size'] == 0, (kname, figures)
-    assert figures['.vgpr_spill_count'] == 0, (kname, figures)
-    assert figures['.sgpr_spill_count'] == 0, (kname, figures)
-    assert 0 < figures['.vgpr_count'] <= 128, (kname, figures)
+  found = resource_figures(text, fused, str(tmp_path / (which + '.hsaco')))
+  for kname, figures in found.items():
+    assert figures['private_segment_fixed_size'] == 0, (kname, figures)
+    assert figures['vgpr_spill_count'] == 0, (kname, figures)
+    assert figures['sgpr_spill_count'] == 0, (kname, figures)
+    assert 0 < figures['vgpr_count'] <= 128, (kname, figures)
 
 
 # ---- planner ------------------------------------------------------------------------------

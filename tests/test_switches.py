@@ -14,7 +14,7 @@ from soda_hip.codegen import backend, host_shim, kernel, kernel_stream2d, switch
 from soda_hip.runtime import host
 
 from conftest import ROOT
-from test_lds3d_codegen import spec_of
+from codegen_util import spec_of
 
 ROWS = switches.SWITCHES
 COMBINATIONS = [dict(zip([s.keyword for s in ROWS], bits))

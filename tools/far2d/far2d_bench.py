@@ -32,39 +32,16 @@ Registers and spills come from the code object's metadata, code sizes from its s
 import argparse
 import json
 import os
-import re
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-for p in (ROOT, os.path.join(ROOT, 'soda-compiler_amd'), os.path.join(ROOT, 'tools')):
+for p in (ROOT, os.path.join(ROOT, 'soda-compiler_amd'), os.path.join(ROOT, 'tools'),
+          os.path.join(ROOT, 'tests')):
   if p not in sys.path:
     sys.path.insert(0, p)
 
-READELF = '/opt/rocm/lib/llvm/bin/llvm-readelf'
 SIZES = {4: (16384, 16384), 8: (8192, 8192)}      # by element size: float, double
-
-
-def static_figures(blob, kname):
-  """VGPRs, SGPRs, scratch and spills of one kernel from the code object's notes."""
-  if not (os.path.exists(READELF) and os.path.exists(blob)):
-    return {}
-  notes = subprocess.check_output([READELF, '--notes', blob]).decode()
-  for block in notes.split('- .agpr_count'):
-    m = re.search(r'\.name:\s+(\S+)', block)
-    if m and m.group(1) == kname:
-      return {k: int(re.search(r'\.%s:\s+(\d+)' % k, block).group(1))
-              for k in ('vgpr_count', 'sgpr_count', 'private_segment_fixed_size',
-                        'vgpr_spill_count', 'sgpr_spill_count')}
-  return {}
-
-
-def code_bytes(blob, kname):
-  """Size of one kernel's code from the code object's symbol table."""
-  symbols = subprocess.check_output([READELF, '-s', blob]).decode()
-  m = re.search(r'^\s*\d+:\s+[0-9a-f]+\s+(\d+)\s+FUNC\s.*\s%s$' % re.escape(kname), symbols, re.M)
-  return int(m.group(1)) if m else 0
 
 
 def main():
@@ -85,6 +62,7 @@ def main():
   from soda_hip import frontend
   from soda_hip.codegen import kernel, switches, spec as specmod
   from soda_hip.runtime import host
+  from codegen_util import code_bytes, static_figures  # tests/: a code object's notes
   apps = args.apps or list(entry.FAR_LANES_APPS)
   iterate = args.iterate
   lines = [

@@ -46,31 +46,14 @@ derived and the compiler's figures and times nothing (no GPU needed).
 import argparse
 import json
 import os
-import re
 import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-for p in (ROOT, os.path.join(ROOT, 'soda-compiler_amd'), os.path.join(ROOT, 'tools')):
+for p in (ROOT, os.path.join(ROOT, 'soda-compiler_amd'), os.path.join(ROOT, 'tools'),
+          os.path.join(ROOT, 'tests')):
   if p not in sys.path:
     sys.path.insert(0, p)
-
-READELF = '/opt/rocm/lib/llvm/bin/llvm-readelf'
-
-
-def static_figures(blob, kname):
-  """VGPRs, SGPRs, LDS, scratch and spills of one kernel from the code object's notes."""
-  if not (os.path.exists(READELF) and os.path.exists(blob)):
-    return {}
-  notes = subprocess.check_output([READELF, '--notes', blob]).decode()
-  for block in notes.split('- .agpr_count'):
-    m = re.search(r'\.name:\s+(\S+)', block)
-    if m and m.group(1) == kname:
-      return {k: int(re.search(r'\.%s:\s+(\d+)' % k, block).group(1))
-              for k in ('vgpr_count', 'sgpr_count', 'group_segment_fixed_size',
-                        'private_segment_fixed_size', 'vgpr_spill_count', 'sgpr_spill_count')}
-  return {}
 
 
 def static_line(kname, f):
@@ -125,6 +108,7 @@ def main():
   import __graft_entry__ as entry
   from soda_hip import frontend
   from soda_hip.codegen import kernel, spec as specmod
+  from codegen_util import static_figures  # tests/: a code object's notes
   apps = args.apps or list(entry.LDS_FIELDS_APPS if args.fields else
                            entry.LDS_RING_APPS if args.ring else entry.LDS3D_APPS)
   if args.fields:
