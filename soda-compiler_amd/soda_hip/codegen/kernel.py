@@ -32,6 +32,9 @@ The unit holds
                         depth-1 kernel;
       2-D, x-neighbours beyond the next lane or windows above 12 rows: kernel_stream2d /
                         kernel_fields2d with chained wave shifts, only with `far_lanes=True`;
+      1-D, x-neighbours beyond the next lane (FIRs of more than 9 float taps, double
+                        stencils of radius 3 and up): kernel_stream1d / kernel_fields1d with
+                        chained wave shifts, only with `far_taps=True`;
   * `soda_hip_meta`, JSON describing the program and the kernel table, which
     libsoda_hip.so reads back from the loaded blob.
 
@@ -165,7 +168,10 @@ RECT3D_INPUT_ROWS = 36
 # depths of the 1-D form (kernel_stream1d), capped by the program's `iterate`: those of
 # fused_depths.  A level is one vector per lane, so no depth is refused for registers; a
 # depth that profiles/r10_stream1d.txt shows not to beat the per-stage schedule leaves
-# this list
+# this list.  Under `far_taps` the same list: every depth a far-tap segment keeps cells at (1, 2
+# and 4 for the samples) beats the per-stage schedule by more than the spread
+# (profiles/r17_far1d.txt, 2^27 cells x 24: the slowest against per stage, lowpass1d depth 4
+# 9.343 against 13.547 ms and acoustic1d depth 1 27.067 against 36.782 ms), so none leaves it
 STREAM1D_DEPTHS = (1, 2, 4, 8, 12)
 STREAM1D_OPTIONS = ('segs',)
 # the 1-D form over several fields (kernel_fields1d) takes the same depths and options
@@ -483,6 +489,7 @@ class Request:
     self.on = {s.keyword: bool(on[s.keyword]) for s in switches.SWITCHES}
     self.meta_notes, self.made = {}, []
     self.far = {}       # what `far_lanes` adds to the 2-D forms' arguments (generate())
+    self.taps = {}      # what `far_taps` adds to the 1-D forms' arguments (generate())
     # one-pass programs with several outputs get the fields forms at depth 1 (opt-in:
     # profiles/r12_rect.txt); such a program is in nobody else's class
     fuse_outputs = self.on['fuse_outputs']
@@ -607,6 +614,57 @@ def far_lanes_depth_limit(spec):
   return max(depths) if depths and made in [k['name'] for k in table] else 0
 
 
+_TAPS_NOT_1D = 'not fused: the far-tap form handles 1-D programs'
+_TAPS_NOT_CONCERNED = 'not concerned: every read within the neighbour lanes'
+
+
+def far_taps_arguments(req):
+  """What `far_taps` adds to the arguments of kernel_stream1d.emit / kernel_fields1d.emit for
+  this request: `hops`, the lanes the lowered program reads away (MAX_HOPS_1D at most:
+  beyond, emit refuses as ever) - for a 1-D program whose stages read beyond the neighbour
+  lane; {} for every other program, whose text then stays what it is.  Leaves in
+  req.meta_notes why a program is not in the class; far_taps_note() says the rest.
+  generate() calls it once, the families read the result as `req.taps`."""
+  if not req.on['far_taps']:
+    return {}
+  key = switches.BY_KEYWORD['far_taps'].note
+  spec = req.spec
+  if spec['dim'] != 1:
+    req.meta_notes[key] = _TAPS_NOT_1D
+    return {}
+  hops = max([1] + [-(-abs(rel[0]) // req.strip['cols'])
+                    for stage in spec['stages'] for _, rel in stage['loads']])
+  if hops == 1:
+    req.meta_notes[key] = _TAPS_NOT_CONCERNED
+    return {}
+  return dict(hops=min(hops, kernel_stream1d.MAX_HOPS_1D))
+
+
+def far_taps_note(req, notes):
+  """The entry `far_taps` of soda_hip_meta for a program in the switch's class: the depth-1
+  kernel made, or why there is none."""
+  if not req.taps:
+    return
+  made = [e['name'] for e in req.made if e['kind'] == 'fused' and e['depth'] == 1]
+  why = [n[len('depth 1 not fused: '):] for n in notes if n.startswith('depth 1 not fused: ')]
+  req.meta_notes[switches.BY_KEYWORD['far_taps'].note] = \
+      made[0] if made else 'not fused: %s' % (why + ['no 1-D form takes it'])[0]
+
+
+def far_taps_depth_limit(spec):
+  """The depth limit under which the entry points of a `far_taps` product run.  The launcher
+  admits fused 1-D kernels, over one array or several, only under a positive limit
+  (csrc/schedule.cpp, plans_fused: no 1-D kernel is in the default schedule), so a 1-D
+  program that the switch gives its kernels runs under the depth of the deepest of them; 0,
+  no limit, for every other program, which runs as it does without the switch."""
+  if spec['dim'] != 1:
+    return 0
+  text, table = generate(spec, far_taps=True)
+  made = kernel_common.read_meta_from_source(text).get(switches.BY_KEYWORD['far_taps'].note)
+  depths = [k['depth'] for k in table if k['kind'] == 'fused']
+  return max(depths) if depths and made in [k['name'] for k in table] else 0
+
+
 def fields2d_kernels(req, notes):
   """Multi-field 2-D programs: kernel_fields2d at each depth; rectangular ones, when
   generate() was asked to fuse their outputs, at depth 1."""
@@ -652,8 +710,8 @@ def fields1d_kernels(req, notes):
   if spec['dim'] != 1 or not kernel_stream2d.multi_field(spec):
     return
   yield from fused_at_depths(req, notes, chain_depths(req), lambda depth: [
-      (kernel_fields1d.emit, dict(form_options('fields1d', req.options),
-                                  cols=req.strip['cols']))])
+      (kernel_fields1d.emit, dict(req.taps, **dict(form_options('fields1d', req.options),
+                                                   cols=req.strip['cols'])))])
 
 
 def stream1d_kernels(req, notes):
@@ -665,8 +723,8 @@ def stream1d_kernels(req, notes):
   if req.depths is not None:
     wanted = sorted(set([1] + [d for d in req.depths if req.chain or d == 1]))
   yield from fused_at_depths(req, notes, wanted, lambda depth: [
-      (kernel_stream1d.emit, dict(form_options('stream1d', req.options),
-                                  cols=req.strip['cols']))])
+      (kernel_stream1d.emit, dict(req.taps, **dict(form_options('stream1d', req.options),
+                                                   cols=req.strip['cols'])))])
 
 
 def stream2d_depths(req):
@@ -991,7 +1049,7 @@ FAMILIES = (fields2d_kernels, fields3d_kernels, fields1d_kernels, stream1d_kerne
 def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
              fused=True, depths=None, inline=True, wave_groups=None,
              fuse_outputs=False, lds_planes=False, lds_fields=False, far_lanes=False,
-             lds_ring=False, **fused_options):
+             lds_ring=False, far_taps=False, **fused_options):
   """Returns (kernel text, kernel table).  `depths` overrides the default set
   of fused depths (depth 1 is always included: the scheduler needs it).
   `fuse_outputs`: a one-pass 2-D / 3-D program with several outputs that is not
@@ -1026,7 +1084,15 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   up to FAR_MAX_PERIOD, at the family's usual depths and under the usual names
   `<app>_fused_k<d>`, in the default schedule; a rectangular one with `fuse_outputs` as well.
   Every other program keeps its table and, apart from the entry `far_lanes` of
-  soda_hip_meta, its text."""
+  soda_hip_meta, its text.
+  `far_taps`: a 1-D program that kernel_stream1d / kernel_fields1d refuse because it reads an
+  x-neighbour beyond the next lane (a float FIR of more than 9 taps, a double stencil of
+  radius 3 and up) gets the same forms with chained wave shifts (`hops`, up to
+  kernel_stream1d.MAX_HOPS_1D lanes), at the family's usual depths and under the usual names
+  `<app>_fused_k<d>`; like every fused 1-D kernel they are launched under a depth limit
+  (switches.depth_limit_of).  Every other program keeps its table and, apart from the entry
+  `far_taps` of soda_hip_meta, its text."""
+  given = locals()      # every row of switches.SWITCHES is a parameter above: read by keyword
   # kernels are generated from the LOWERED program (pointwise-only locals folded
   # into their readers); the blob is still identified by the source program
   source = spec
@@ -1042,16 +1108,16 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   parts.append(text)
   notes = []
   req = Request(spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
-                fused_options, dict(fuse_outputs=fuse_outputs, lds_planes=lds_planes,
-                                    lds_fields=lds_fields, far_lanes=far_lanes,
-                                    lds_ring=lds_ring))
+                fused_options, {s.keyword: given[s.keyword] for s in switches.SWITCHES})
   req.far = far_lanes_arguments(req)
+  req.taps = far_taps_arguments(req)
   for family in FAMILIES if fused else ():
     for ftext, entry in family(req, notes):
       parts.append(ftext)
       table.append(annotate_cost(entry, spec))
       req.made.append(entry)
   far_lanes_note(req, notes)
+  far_taps_note(req, notes)
   if notes:
     parts.append(''.join('// %s\n' % n for n in notes))
   extra = dict(program_hash=kernel_common.program_hash(source),

@@ -21,11 +21,17 @@ are issued before the first level.  What this form adds is kernel_fields2d's x h
     segments all lie inside the array loads whole vectors (INTERIOR), any other takes the
     guarded path where cells outside the array read as 0.  Such values reach only cells
     outside every output's box (boxes are the composed windows).
+
+`hops` (the far-tap form, kernel.generate's `far_taps`) is kernel_stream1d's: x-neighbours up
+to `hops` lanes away through chained wave shifts.  What a shift delivers to the first and
+last `hops` lanes of a wavefront falls inside the padded halo, which is the hull of the
+composed windows of all fields: a wrong cell is one whose reads, level by level, left the
+segment.
 """
 
 from . import spec as specmod
 from .kernel_common import builtin_type, cell_assignment, tensor_index
-from .kernel_stream1d import Level, emit_vector_load, geometry
+from .kernel_stream1d import Level, check_reach, emit_vector_load, far_vgprs, geometry
 from .kernel_stream2d import (LANES, WAVES_PER_BLOCK, NotFusable, kernel_name,
                               lane_operand, multi_field)
 
@@ -97,8 +103,9 @@ def build_levels(spec, depth):
   return levels, [current[o] for o in spec['outputs']]
 
 
-def emit(spec, depth, cols=None, segs=None):
-  """Returns (text, kernel table entry) for one fused depth of a multi-field 1-D program."""
+def emit(spec, depth, cols=None, segs=None, hops=1):
+  """Returns (text, kernel table entry) for one fused depth of a multi-field 1-D program.
+  hops: how many lanes away an x-neighbour may lie (1 .. kernel_stream1d.MAX_HOPS_1D)."""
   levels, finals = build_levels(spec, depth)
   N = len(finals)
   elem = specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
@@ -108,11 +115,7 @@ def emit(spec, depth, cols=None, segs=None):
   segs = default_segs(N) if segs is None else int(segs)
   if segs < 1:
     raise ValueError('segs: %r' % (segs,))
-  for level in levels:
-    for (_, rel) in level.reads:
-      if abs(rel[0]) > cols:
-        raise NotFusable('x offset %d exceeds the %d columns a lane holds'
-                         % (rel[0], cols))
+  check_reach(levels, cols, hops)
   geo = geometry(spec, depth, cols)
   index = tensor_index(spec)
   name = kernel_name(spec, depth)
@@ -122,7 +125,9 @@ def emit(spec, depth, cols=None, segs=None):
   # vectors of all fields of all segments, three iterations' worth of levels of one segment
   # (one being read, one being written, the finals) and ten plus two per output for
   # addresses and ranges.
-  est_vgprs = segs * N * -(-C * elem // 4) + 3 * N * C * regs + 10 + 2 * N
+  # Reads beyond the neighbour lane add kernel_stream1d.far_vgprs (0 without them).
+  est_vgprs = segs * N * -(-C * elem // 4) + 3 * N * C * regs + 10 + 2 * N + \
+      far_vgprs(levels, C)
 
   o = []
   emit_line = o.append

@@ -25,6 +25,13 @@ reach only cells outside the launch's box (the box is the composed window).  Sto
 to the box intersected with the segment's own w_out cells, as a per-lane range of its C
 cells.  Vector accesses are declared aligned to the element only: the caller's arrays
 start anywhere.
+
+`hops` (the far-tap form, kernel.generate's `far_taps`): an x-neighbour may lie up to `hops`
+lanes away, lane_operand chaining one wave shift per lane; one hop prints the text above.
+What a shift delivers to the first and last `hops` lanes of a wavefront falls inside the
+padded halo: a cell is wrong only where a read of its level, or of a level below it, left
+the segment, so the wrong cells at either end are at most the window composed so far, and
+the halo is that window over all `depth` iterations padded up to whole vectors.
 """
 
 from . import spec as specmod
@@ -33,6 +40,14 @@ from .kernel_stream2d import (LANES, WAVES_PER_BLOCK, NotFusable, kernel_name,
                               lane_operand)
 
 DEFAULT_SEGS = 4
+# lanes an x-neighbour may lie away in the far-tap form (emit's `hops`).  The chain is cheap:
+# every link of a chain of wave shifts is itself an operand some nearer tap reads, so a window
+# of radius R lanes costs about 2R moves per column and level next to its 2(2R + 1) arithmetic
+# operations, and a level stays C registers at any depth.  What bounds the form is the halo:
+# a segment of 64 lanes loses `hops` of them per side, level and iteration.  At 8 lanes per
+# side a float depth-1 segment still keeps 192 of 256 cells and depth 2 half of them; beyond
+# that the halo, not the chain, makes the form pointless.
+MAX_HOPS_1D = 8
 
 
 class Level:
@@ -91,6 +106,47 @@ def geometry(spec, depth, cols):
               origin_align=cols)
 
 
+def check_reach(levels, cols, hops):
+  """kernel_stream2d.check_reach for levels: `hops` in 1 .. MAX_HOPS_1D, every read within
+  `hops` lanes."""
+  if not 1 <= hops <= MAX_HOPS_1D:
+    raise ValueError('hops: %r' % (hops,))
+  for level in levels:
+    for (_, rel) in level.reads:
+      if abs(rel[0]) > hops * cols:
+        raise NotFusable('x offset %d exceeds the %d columns a lane holds'
+                         % (rel[0], cols))
+
+
+def far_vgprs(levels, cols):
+  """What reads beyond the neighbour lane keep alive while a level is computed, in 32-bit
+  words: 0 for a program without them.  A wave shift folds into the operation that consumes
+  it, a chain of shifts does not: every link beyond the first is a move into a register of
+  its own, shared by the cells that read the same column through it.  A link stays alive
+  while a cell of the level still has to read it; one that only leads on to the next link
+  lives for one move.  Per level, the distinct links some cell reads - per source, side,
+  column and lane beyond the first - and one level of partial sums in flight; the levels run
+  one after the other, so the costliest one counts.  In a full window (lowpass1d, dfir1d,
+  acoustic1d) every link is read: 2 sides x C columns x (lanes - 1); in a sparse one
+  (skewfir1d's three taps) only the chains' ends are.  Held against the compiler's counts
+  (hipcc 7.2, gfx950; extra over the estimate without this term, at every depth): lowpass1d
+  28 against +26, dfir1d 28 against +26, skewfir1d 14 against +2 / +0, acoustic1d 28 where
+  the whole kernel stays 8 under the estimate without it.  tests/test_far1d_codegen.py holds
+  every shipped kernel to its estimate."""
+  worst = 0
+  for level in levels:
+    links = {}
+    for (tensor, rel), src in level.reads.items():
+      for j in range(rel[0], rel[0] + cols):
+        if abs(j // cols) >= 2:
+          links[id(src), j < 0, j % cols, abs(j // cols)] = \
+              max(1, specmod.ELEM_SIZE[src.c_type] // 4)
+    if links:
+      worst = max(worst, sum(links.values()) +
+                  cols * max(1, specmod.ELEM_SIZE[level.c_type] // 4))
+  return worst
+
+
 def emit_vector_load(emit_line, function, vec, T, C, elem):
   """The vector type `vec` of C cells of T, aligned to the element only, and the load of
   one lane's vector through it: whole when the wavefront is INTERIOR, else cell by cell
@@ -109,8 +165,10 @@ def emit_vector_load(emit_line, function, vec, T, C, elem):
   emit_line('}')
 
 
-def emit(spec, depth, cols=None, segs=DEFAULT_SEGS):
-  """Returns (text, kernel table entry) for one fused depth of a 1-D program."""
+def emit(spec, depth, cols=None, segs=DEFAULT_SEGS, hops=1):
+  """Returns (text, kernel table entry) for one fused depth of a 1-D program.  hops: how many
+  lanes away an x-neighbour may lie (1 .. MAX_HOPS_1D; one hop prints the neighbour-lane
+  text)."""
   levels = build_levels(spec, depth)
   in_type = spec['inputs'][0]['c_type']
   elem = specmod.ELEM_SIZE[in_type]
@@ -120,11 +178,7 @@ def emit(spec, depth, cols=None, segs=DEFAULT_SEGS):
   segs = int(segs)
   if segs < 1:
     raise ValueError('segs: %r' % (segs,))
-  for level in levels:
-    for (_, rel) in level.reads:
-      if abs(rel[0]) > cols:
-        raise NotFusable('x offset %d exceeds the %d columns a lane holds'
-                         % (rel[0], cols))
+  check_reach(levels, cols, hops)
   geo = geometry(spec, depth, cols)
   index = tensor_index(spec)
   name = kernel_name(spec, depth)
@@ -136,7 +190,8 @@ def emit(spec, depth, cols=None, segs=DEFAULT_SEGS):
   # vectors of all segments (16 bytes = 4 registers each at the default C), two levels of
   # one segment unpacked to a register (pair) per cell, and ten for addresses and ranges.
   # Compiled: float and double 34 at segs = 4, 58 at segs = 8; uint16 about 50.
-  est_vgprs = segs * -(-C * elem // 4) + 2 * C * max(1, elem // 4) + 10
+  # Reads beyond the neighbour lane add far_vgprs (0 without them).
+  est_vgprs = segs * -(-C * elem // 4) + 2 * C * max(1, elem // 4) + 10 + far_vgprs(levels, C)
 
   o = []
   emit_line = o.append

@@ -28,6 +28,12 @@ SWITCHES = (
            'for a 3-D program with two or three outputs that read inputs only '
            '(launched under a depth limit of 1: soda_hip_plan_set_max_depth)',
            '.ldsf', True, 'lds_fields'),
+    Switch('far_taps', '--hip-far-taps', 'hip_far_taps',
+           'the fused 1-D kernels for a program that reads an x-neighbour beyond the next '
+           'lane (float FIRs of more than 9 taps, double stencils of radius 3 and up): the '
+           'same forms with chained wave shifts, up to 8 lanes away.  Fused 1-D kernels are '
+           'not in the default schedule: the program is launched under the depth limit of '
+           'its deepest kernel (soda_hip_plan_set_max_depth)', '.taps', False, 'far_taps'),
     Switch('far_lanes', '--hip-far-lanes', 'hip_far_lanes',
            'the fused 2-D kernels for a program that reads an x-neighbour beyond the next '
            'lane or keeps a window above 12 rows (float stars of radius 5 and up, double '
@@ -72,13 +78,17 @@ def depth_limit_of(spec, on):
   """The depth limit the entry points generated for `spec` with the switches `on` set before
   they run, and the flags that ask for it: (0, []) for none.  1 where a switch makes a fused
   kernel over several outputs; under `far_lanes`, for a program over several fields that the
-  switch gives its kernels, the depth of the deepest (kernel.far_lanes_depth_limit)."""
+  switch gives its kernels, the depth of the deepest (kernel.far_lanes_depth_limit); under
+  `far_taps`, the same for a 1-D program over one array or several
+  (kernel.far_taps_depth_limit).  The two concern disjoint programs."""
   if depth_limit(on):
     return 1, depth_limit_flags(on)
-  if on.get('far_lanes'):
-    from . import kernel
-    limit = kernel.far_lanes_depth_limit(spec)
-    return limit, [BY_KEYWORD['far_lanes'].flag] if limit else []
+  from . import kernel
+  for keyword, limit_of in (('far_lanes', kernel.far_lanes_depth_limit),
+                            ('far_taps', kernel.far_taps_depth_limit)):
+    limit = limit_of(spec) if on.get(keyword) else 0
+    if limit:
+      return limit, [BY_KEYWORD[keyword].flag]
   return 0, []
 
 

@@ -7,8 +7,8 @@ selection must give zero differing lines, the error lines included).
 
 The opt-in switches of generate() (fuse_outputs, lds_planes, lds_fields, lds_ring) are cases
 too (the cases of the first three are printed first and as they were before `lds_ring`
-existed, those with `lds_ring` after them, those with `far_lanes` after these: an older
-tree's output is a prefix-wise subset), and
+existed, those with `lds_ring` after them, those with `far_lanes` after these, those with
+`far_taps` last: an older tree's output is a prefix-wise subset), and
 what is derived from them outside the generator has lines of its own: `host/...`, the sha256
 of the generated Python and C++ host texts per combination of switches, and `file/...`, the
 name of the prebuilt code object per combination build() uses.
@@ -104,6 +104,7 @@ LDS_SAMPLES = [(app, dict(lds_planes=True)) for app in lds3d.APPS] + [
     (app, lds3d_fields.switches(app)) for app in lds3d_fields.APPS]
 RING_SAMPLES = [(app, dict(lds_ring=True)) for app in entry.LDS_RING_APPS]
 FAR_SAMPLES = [(app, dict(far_lanes=True)) for app in entry.FAR_LANES_APPS]
+TAPS_SAMPLES = [(app, dict(far_taps=True)) for app in entry.FAR_TAPS_APPS]
 HOST_PROGRAMS = ('jacobi2d', 'grad2d', 'grad3d', 'star3d', 'acoustic3d', 'deriv3d')
 HOST_CPP_SWITCHES = ('fuse_outputs', 'lds_fields')      # the keywords host_cpp.print_code took
 
@@ -250,6 +251,23 @@ def cases():
     make = lambda t=text: specmod.spec_from_stencil(frontend.loads(t))
     for on in with_far:
       yield 'inline/%s/%s' % (key, show(on)), make, on
+  # `far_taps`: alone and with the other five on every sample and program text, and its
+  # samples at the iteration counts that change their depths (8: a segment keeps no cells)
+  with_taps = [dict(far_taps=True), dict({n: True for n in SWITCHES}, far_lanes=True,
+                                         far_taps=True)]
+  for path in sorted(glob.glob(os.path.join(SAMPLES, '*.soda')) +
+                     glob.glob(os.path.join(SAMPLES, 'extra', '*.soda'))):
+    app = os.path.basename(path)[:-5]
+    for on in with_taps:
+      yield 'switch/%s/%s' % (app, show(on)), (lambda a=app: spec_of(a, None)), on
+  for app, on in TAPS_SAMPLES:
+    for iterate in (1, 2, 3, 8, None):
+      yield 'taps_iterate/%s/%s' % (app, iterate), (lambda a=app, i=iterate: spec_of(a, i)), on
+    yield 'taps_cols/%s' % app, (lambda a=app: spec_of(a, None)), dict(on, cols=8)
+  for key, text in inline_texts():
+    make = lambda t=text: specmod.spec_from_stencil(frontend.loads(t))
+    for on in with_taps:
+      yield 'inline/%s/%s' % (key, show(on)), make, on
 
 
 def digest(text):
@@ -292,6 +310,13 @@ def host_lines():
     yield 'host/shim/%s/far_lanes %s' % (app, digest(out.getvalue()))
   for on in ({}, dict(far_lanes=True)):
     for app in entry.FAR_LANES_APPS:
+      yield 'file/%s/%s %s' % (app, show(on), os.path.basename(entry.blob_path(app, **on)))
+  for app in HOST_PROGRAMS + entry.FAR_TAPS_APPS:
+    out = io.StringIO()
+    host_shim.print_code(spec_of(app, None), out, far_taps=True)
+    yield 'host/shim/%s/far_taps %s' % (app, digest(out.getvalue()))
+  for on in ({}, dict(far_taps=True)):
+    for app in entry.FAR_TAPS_APPS:
       yield 'file/%s/%s %s' % (app, show(on), os.path.basename(entry.blob_path(app, **on)))
 
 
