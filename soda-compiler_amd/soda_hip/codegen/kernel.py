@@ -40,7 +40,8 @@ The unit holds
 
 generate() is the driver: one function per family (FAMILIES) selects forms, depths and
 options, form_options() says which options a form receives.  The opt-in forms' switches
-are the rows of switches.py.
+are the rows of switches.py; what differs between the forms of a kind, the rows of LdsForm
+(the LDS-plane forms) and of FAR_FORMS (the far-reach forms).
 """
 import collections
 import functools
@@ -488,8 +489,9 @@ class Request:
     # far: an LDS-plane form is emitted only where they hold no fused depth-1 kernel
     self.on = {s.keyword: bool(on[s.keyword]) for s in switches.SWITCHES}
     self.meta_notes, self.made = {}, []
-    self.far = {}       # what `far_lanes` adds to the 2-D forms' arguments (generate())
-    self.taps = {}      # what `far_taps` adds to the 1-D forms' arguments (generate())
+    # what a far-reach switch adds to the arguments of its dimensionality's forms (FAR_FORMS;
+    # generate()): the switches concern programs of different dimensionality, so one dict
+    self.far = {}
     # one-pass programs with several outputs get the fields forms at depth 1 (opt-in:
     # profiles/r12_rect.txt); such a program is in nobody else's class
     fuse_outputs = self.on['fuse_outputs']
@@ -551,116 +553,87 @@ def fused_at_depths(req, notes, wanted, attempts_of):
       return
 
 
-_FAR_NOT_2D = 'not fused: the far-lane form handles 2-D programs'
-_FAR_NOT_CONCERNED = 'not concerned: every read within the neighbour lanes and %d rows'
+# The far-reach forms, one per switch: the fused forms of one dimensionality with x-neighbours
+# beyond the next lane (chained wave shifts, emit's `hops`).  `name`: of the form in notes.
+# `max_hops`: the lanes its emit() takes.  `window_rows`: for forms that also widen the row
+# window (2-D: up to FAR_MAX_PERIOD rows), the rows the depth-1 pipeline keeps for the request;
+# None where there is no window.  `needs_limit`: the programs whose fused kernels are outside
+# the default schedule, so that a product of the switch runs under a depth limit
+# (far_depth_limit).
+FarForm = collections.namedtuple('FarForm', 'switch dim name max_hops window_rows needs_limit')
 
 
-def far_lanes_arguments(req):
-  """What `far_lanes` adds to the arguments of kernel_stream2d.emit / kernel_fields2d.emit for
-  this request: `hops`, the lanes the lowered program reads away (MAX_HOPS at most: beyond,
-  emit refuses as ever), and FAR_MAX_PERIOD - for a 2-D program that those forms refuse a
-  depth-1 kernel today for an x offset beyond the neighbour lane or for a window above their
-  period limit; {} for every other program, whose text then stays what it is.  Leaves in
-  req.meta_notes why a program is not in the class; far_lanes_note() says the rest.
-  generate() calls it once, the families read the result as `req.far`."""
-  if not req.on['far_lanes']:
-    return {}
-  key = switches.BY_KEYWORD['far_lanes'].note
+def window_rows_2d(req):
+  """Rows of the widest window the 2-D forms' depth-1 pipeline keeps for this request."""
   spec = req.spec
-  if spec['dim'] != 2:
-    req.meta_notes[key] = _FAR_NOT_2D
-    return {}
-  limit = kernel_stream2d.DEFAULT_MAX_PERIOD
-  hops = max([1] + [-(-abs(rel[0]) // req.strip['cols'])
-                    for stage in spec['stages'] for _, rel in stage['loads']])
   try:
     fields = kernel_stream2d.multi_field(spec) or kernel_stream2d.rectangular(spec)
     insts, _ = kernel_stream2d.build_pipeline(spec, 1, req.strip['prefetch'], fields=fields)
-    rows = max(inst.keep for inst in insts)
+    return max(inst.keep for inst in insts)
   except kernel_stream2d.NotFusable:
-    rows = 0          # no 2-D form takes it, whatever its reach: refused as ever
-  if hops == 1 and rows <= req.options.get('max_period', limit):
-    req.meta_notes[key] = _FAR_NOT_CONCERNED % limit
+    return 0          # no 2-D form takes it, whatever its reach: refused as ever
+
+
+FAR_FORMS = (
+    FarForm('far_lanes', 2, 'far-lane', kernel_stream2d.MAX_HOPS, window_rows_2d,
+            kernel_stream2d.multi_field),
+    FarForm('far_taps', 1, 'far-tap', kernel_stream1d.MAX_HOPS_1D, None, lambda spec: True))
+
+
+def far_arguments(form, req):
+  """What the form's switch adds to the arguments of its dimensionality's emit()s for this
+  request: `hops`, the lanes the lowered program reads away (form.max_hops at most: beyond,
+  emit refuses as ever), and for a windowed form FAR_MAX_PERIOD - for a program of the form's
+  dimensionality that those emit()s refuse a depth-1 kernel today for an x offset beyond the
+  neighbour lane or for a window above their period limit; {} for every other program, whose
+  text then stays what it is.  Leaves in req.meta_notes why a program is not in the class;
+  far_note() says the rest.  generate() collects the results in `req.far`."""
+  spec = req.spec
+  if not req.on[form.switch]:
+    return {}
+  key = switches.BY_KEYWORD[form.switch].note
+  if spec['dim'] != form.dim:
+    req.meta_notes[key] = 'not fused: the %s form handles %d-D programs' % (form.name, form.dim)
+    return {}
+  limit = kernel_stream2d.DEFAULT_MAX_PERIOD
+  hops = max([1] + [kernel_stream2d.lanes_away(rel[0], req.strip['cols'])
+                    for stage in spec['stages'] for _, rel in stage['loads']])
+  if hops == 1 and not (form.window_rows and
+                        form.window_rows(req) > req.options.get('max_period', limit)):
+    req.meta_notes[key] = 'not concerned: every read within the neighbour lanes%s' % (
+        ' and %d rows' % limit if form.window_rows else '')
     return {}
   if kernel_stream2d.rectangular(spec) and not req.rect:
     req.meta_notes[key] = _NOT_RECT[1]
     return {}
-  return dict(hops=min(hops, kernel_stream2d.MAX_HOPS), max_period=FAR_MAX_PERIOD)
+  return dict(hops=min(hops, form.max_hops),
+              **(dict(max_period=FAR_MAX_PERIOD) if form.window_rows else {}))
 
 
-def far_lanes_note(req, notes):
-  """The entry `far_lanes` of soda_hip_meta for a program in the switch's class: the depth-1
-  kernel made, or why there is none."""
-  key = switches.BY_KEYWORD['far_lanes'].note
-  if not req.far:
+def far_note(form, req, notes):
+  """The switch's entry of soda_hip_meta for a program in its class: the depth-1 kernel made,
+  or why there is none.  (req.far is shared: a program of the other form's dimensionality is
+  not this form's to speak of.)"""
+  if not (req.on[form.switch] and req.spec['dim'] == form.dim and req.far):
     return
   made = [e['name'] for e in req.made if e['kind'] == 'fused' and e['depth'] == 1]
   why = [n[len('depth 1 not fused: '):] for n in notes if n.startswith('depth 1 not fused: ')]
-  req.meta_notes[key] = made[0] if made else 'not fused: %s' % (why + ['no 2-D form takes it'])[0]
+  req.meta_notes[switches.BY_KEYWORD[form.switch].note] = made[0] if made else \
+      'not fused: %s' % (why + ['no %d-D form takes it' % form.dim])[0]
 
 
-def far_lanes_depth_limit(spec):
-  """The depth limit under which the entry points of a `far_lanes` product run.  The
-  launcher admits fused kernels over several fields only under a positive limit
-  (csrc/schedule.cpp, plans_fused), so a program over several fields that the switch gives
-  its kernels runs under the depth of the deepest of them; 0, no limit, for every other
-  program - a single-array program's kernels are in the default schedule, and a multi-field
-  program outside the switch's class runs as it does without the switch."""
-  if spec['dim'] != 2 or not kernel_stream2d.multi_field(spec):
+def far_depth_limit(form, spec):
+  """The depth limit under which the entry points of a product of the form's switch run.  The
+  launcher admits fused kernels outside the default schedule - those over several fields, and
+  every 1-D one - only under a positive limit (csrc/schedule.cpp, plans_fused), so a program
+  of form.needs_limit that the switch gives its kernels runs under the depth of the deepest
+  of them; 0, no limit, for every other program - a single-array 2-D program's kernels are in
+  the default schedule, and a program outside the switch's class runs as it does without the
+  switch."""
+  if spec['dim'] != form.dim or not form.needs_limit(spec):
     return 0
-  text, table = generate(spec, far_lanes=True)
-  made = kernel_common.read_meta_from_source(text).get(switches.BY_KEYWORD['far_lanes'].note)
-  depths = [k['depth'] for k in table if k['kind'] == 'fused']
-  return max(depths) if depths and made in [k['name'] for k in table] else 0
-
-
-_TAPS_NOT_1D = 'not fused: the far-tap form handles 1-D programs'
-_TAPS_NOT_CONCERNED = 'not concerned: every read within the neighbour lanes'
-
-
-def far_taps_arguments(req):
-  """What `far_taps` adds to the arguments of kernel_stream1d.emit / kernel_fields1d.emit for
-  this request: `hops`, the lanes the lowered program reads away (MAX_HOPS_1D at most:
-  beyond, emit refuses as ever) - for a 1-D program whose stages read beyond the neighbour
-  lane; {} for every other program, whose text then stays what it is.  Leaves in
-  req.meta_notes why a program is not in the class; far_taps_note() says the rest.
-  generate() calls it once, the families read the result as `req.taps`."""
-  if not req.on['far_taps']:
-    return {}
-  key = switches.BY_KEYWORD['far_taps'].note
-  spec = req.spec
-  if spec['dim'] != 1:
-    req.meta_notes[key] = _TAPS_NOT_1D
-    return {}
-  hops = max([1] + [-(-abs(rel[0]) // req.strip['cols'])
-                    for stage in spec['stages'] for _, rel in stage['loads']])
-  if hops == 1:
-    req.meta_notes[key] = _TAPS_NOT_CONCERNED
-    return {}
-  return dict(hops=min(hops, kernel_stream1d.MAX_HOPS_1D))
-
-
-def far_taps_note(req, notes):
-  """The entry `far_taps` of soda_hip_meta for a program in the switch's class: the depth-1
-  kernel made, or why there is none."""
-  if not req.taps:
-    return
-  made = [e['name'] for e in req.made if e['kind'] == 'fused' and e['depth'] == 1]
-  why = [n[len('depth 1 not fused: '):] for n in notes if n.startswith('depth 1 not fused: ')]
-  req.meta_notes[switches.BY_KEYWORD['far_taps'].note] = \
-      made[0] if made else 'not fused: %s' % (why + ['no 1-D form takes it'])[0]
-
-
-def far_taps_depth_limit(spec):
-  """The depth limit under which the entry points of a `far_taps` product run.  The launcher
-  admits fused 1-D kernels, over one array or several, only under a positive limit
-  (csrc/schedule.cpp, plans_fused: no 1-D kernel is in the default schedule), so a 1-D
-  program that the switch gives its kernels runs under the depth of the deepest of them; 0,
-  no limit, for every other program, which runs as it does without the switch."""
-  if spec['dim'] != 1:
-    return 0
-  text, table = generate(spec, far_taps=True)
-  made = kernel_common.read_meta_from_source(text).get(switches.BY_KEYWORD['far_taps'].note)
+  text, table = generate(spec, **{form.switch: True})
+  made = kernel_common.read_meta_from_source(text).get(switches.BY_KEYWORD[form.switch].note)
   depths = [k['depth'] for k in table if k['kind'] == 'fused']
   return max(depths) if depths and made in [k['name'] for k in table] else 0
 
@@ -710,7 +683,7 @@ def fields1d_kernels(req, notes):
   if spec['dim'] != 1 or not kernel_stream2d.multi_field(spec):
     return
   yield from fused_at_depths(req, notes, chain_depths(req), lambda depth: [
-      (kernel_fields1d.emit, dict(req.taps, **dict(form_options('fields1d', req.options),
+      (kernel_fields1d.emit, dict(req.far, **dict(form_options('fields1d', req.options),
                                                    cols=req.strip['cols'])))])
 
 
@@ -723,7 +696,7 @@ def stream1d_kernels(req, notes):
   if req.depths is not None:
     wanted = sorted(set([1] + [d for d in req.depths if req.chain or d == 1]))
   yield from fused_at_depths(req, notes, wanted, lambda depth: [
-      (kernel_stream1d.emit, dict(req.taps, **dict(form_options('stream1d', req.options),
+      (kernel_stream1d.emit, dict(req.far, **dict(form_options('stream1d', req.options),
                                                    cols=req.strip['cols'])))])
 
 
@@ -743,7 +716,7 @@ def stream2d_depths(req):
 
 def stream2d_single(req, depth, strip, notes, far):
   """The single-wave kernel of this depth (kernel_stream2d), or None with a note.  far: what
-  far_lanes_arguments() adds to the form's arguments."""
+  far_arguments() adds to the form's arguments."""
   # the memory-bound depths store around the caches when a launch's box
   # does not fit the Infinity Cache (kernel_stream2d.emit: nontemporal)
   options = dict({'nontemporal': 4} if depth <= NT_AUTO_MAX_DEPTH_2D else {},
@@ -1109,15 +1082,15 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   notes = []
   req = Request(spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
                 fused_options, {s.keyword: given[s.keyword] for s in switches.SWITCHES})
-  req.far = far_lanes_arguments(req)
-  req.taps = far_taps_arguments(req)
+  for form in FAR_FORMS:
+    req.far.update(far_arguments(form, req))
   for family in FAMILIES if fused else ():
     for ftext, entry in family(req, notes):
       parts.append(ftext)
       table.append(annotate_cost(entry, spec))
       req.made.append(entry)
-  far_lanes_note(req, notes)
-  far_taps_note(req, notes)
+  for form in FAR_FORMS:
+    far_note(form, req, notes)
   if notes:
     parts.append(''.join('// %s\n' % n for n in notes))
   extra = dict(program_hash=kernel_common.program_hash(source),

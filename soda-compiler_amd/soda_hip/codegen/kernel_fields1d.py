@@ -31,8 +31,8 @@ segment.
 
 from . import spec as specmod
 from .kernel_common import builtin_type, cell_assignment, tensor_index
-from .kernel_stream1d import Level, check_reach, emit_vector_load, far_vgprs, geometry
-from .kernel_stream2d import (LANES, WAVES_PER_BLOCK, NotFusable, kernel_name,
+from .kernel_stream1d import MAX_HOPS_1D, Level, emit_vector_load, far_vgprs, geometry
+from .kernel_stream2d import (LANES, WAVES_PER_BLOCK, NotFusable, check_reach, kernel_name,
                               lane_operand, multi_field)
 
 # soda_hip_args.param[1..2]: two 8-bit extras per output, four outputs to a word
@@ -115,7 +115,7 @@ def emit(spec, depth, cols=None, segs=None, hops=1):
   segs = default_segs(N) if segs is None else int(segs)
   if segs < 1:
     raise ValueError('segs: %r' % (segs,))
-  check_reach(levels, cols, hops)
+  check_reach(levels, cols, hops, MAX_HOPS_1D)
   geo = geometry(spec, depth, cols)
   index = tensor_index(spec)
   name = kernel_name(spec, depth)

@@ -36,7 +36,7 @@ the halo is that window over all `depth` iterations padded up to whole vectors.
 
 from . import spec as specmod
 from .kernel_common import builtin_type, cell_assignment, tensor_index
-from .kernel_stream2d import (LANES, WAVES_PER_BLOCK, NotFusable, kernel_name,
+from .kernel_stream2d import (LANES, WAVES_PER_BLOCK, NotFusable, check_reach, kernel_name,
                               lane_operand)
 
 DEFAULT_SEGS = 4
@@ -106,18 +106,6 @@ def geometry(spec, depth, cols):
               origin_align=cols)
 
 
-def check_reach(levels, cols, hops):
-  """kernel_stream2d.check_reach for levels: `hops` in 1 .. MAX_HOPS_1D, every read within
-  `hops` lanes."""
-  if not 1 <= hops <= MAX_HOPS_1D:
-    raise ValueError('hops: %r' % (hops,))
-  for level in levels:
-    for (_, rel) in level.reads:
-      if abs(rel[0]) > hops * cols:
-        raise NotFusable('x offset %d exceeds the %d columns a lane holds'
-                         % (rel[0], cols))
-
-
 def far_vgprs(levels, cols):
   """What reads beyond the neighbour lane keep alive while a level is computed, in 32-bit
   words: 0 for a program without them.  A wave shift folds into the operation that consumes
@@ -178,7 +166,7 @@ def emit(spec, depth, cols=None, segs=DEFAULT_SEGS, hops=1):
   segs = int(segs)
   if segs < 1:
     raise ValueError('segs: %r' % (segs,))
-  check_reach(levels, cols, hops)
+  check_reach(levels, cols, hops, MAX_HOPS_1D)
   geo = geometry(spec, depth, cols)
   index = tensor_index(spec)
   name = kernel_name(spec, depth)

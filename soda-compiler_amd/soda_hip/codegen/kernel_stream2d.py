@@ -206,20 +206,32 @@ def rotation_period(insts, max_period):
   return best[1]
 
 
+def lanes_away(dx, cols):
+  """Lanes between a lane of `cols` columns and the one that holds its x-neighbour `dx`."""
+  return -(-abs(dx) // cols)
+
+
+def read_x_offsets(reader):
+  """The x offsets a reader reads at: an Instance lists (source, offset, ...), a
+  kernel_stream1d.Level maps (tensor, offset) to the source."""
+  return [read[1][0] for read in reader.reads]
+
+
 def far_hops(insts, cols):
   """Lanes away the farthest x-neighbour of the pipeline lies (lane_operand): 1 for every
   program the neighbour-lane forms take."""
-  return max([1] + [-(-abs(rel[0]) // cols) for inst in insts for _, rel, _ in inst.reads])
+  return max([1] + [lanes_away(dx, cols) for inst in insts for dx in read_x_offsets(inst)])
 
 
-def check_reach(insts, cols, hops):
-  if not 1 <= hops <= MAX_HOPS:
+def check_reach(readers, cols, hops, max_hops=MAX_HOPS):
+  """`hops` in 1 .. max_hops, and every read of the readers (instances or 1-D levels) within
+  `hops` lanes."""
+  if not 1 <= hops <= max_hops:
     raise ValueError('hops: %r' % (hops,))
-  for inst in insts:
-    for src, rel, _ in inst.reads:
-      if abs(rel[0]) > hops * cols:
-        raise NotFusable('x offset %d exceeds the %d columns a lane holds'
-                         % (rel[0], cols))
+  for reader in readers:
+    for dx in read_x_offsets(reader):
+      if abs(dx) > hops * cols:
+        raise NotFusable('x offset %d exceeds the %d columns a lane holds' % (dx, cols))
 
 
 def estimated_vgprs(insts, cols):

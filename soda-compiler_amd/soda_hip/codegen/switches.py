@@ -3,7 +3,9 @@
 A switch is a boolean keyword of generate() that adds one kernel form to the programs in its
 class.  Everything outside the generator that has to know a switch - the command line, the
 generated hosts, the run-time's depth limit, the name of the prebuilt code object - reads it
-here: an opt-in form more is a row more.  Data and pure functions only.
+here: an opt-in form more is a row more.  Data and pure functions only.  (The far-reach
+switches' depth limit depends on the program: depth_limit_of reads it off kernel.FAR_FORMS,
+where such a form is a row as well.)
 """
 import collections
 
@@ -77,18 +79,18 @@ def depth_limit(on):
 def depth_limit_of(spec, on):
   """The depth limit the entry points generated for `spec` with the switches `on` set before
   they run, and the flags that ask for it: (0, []) for none.  1 where a switch makes a fused
-  kernel over several outputs; under `far_lanes`, for a program over several fields that the
-  switch gives its kernels, the depth of the deepest (kernel.far_lanes_depth_limit); under
-  `far_taps`, the same for a 1-D program over one array or several
-  (kernel.far_taps_depth_limit).  The two concern disjoint programs."""
+  kernel over several outputs; under a far-reach switch (the rows of kernel.FAR_FORMS, in
+  that order: `far_lanes`, `far_taps`), for a program whose fused kernels the switch makes
+  and the default schedule does not hold - 2-D over several fields, 1-D over one array or
+  several - the depth of the deepest (kernel.far_depth_limit).  The far-reach switches
+  concern disjoint programs."""
   if depth_limit(on):
     return 1, depth_limit_flags(on)
   from . import kernel
-  for keyword, limit_of in (('far_lanes', kernel.far_lanes_depth_limit),
-                            ('far_taps', kernel.far_taps_depth_limit)):
-    limit = limit_of(spec) if on.get(keyword) else 0
+  for form in kernel.FAR_FORMS:
+    limit = kernel.far_depth_limit(form, spec) if on.get(form.switch) else 0
     if limit:
-      return limit, [BY_KEYWORD[keyword].flag]
+      return limit, [BY_KEYWORD[form.switch].flag]
   return 0, []
 
 

@@ -425,7 +425,7 @@ def test_sodac_writes_all_products_with_the_switch(tmp_path):
 
 
 def test_the_measurement_tool_prints_its_usage():
-  r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'far2d', 'far2d_bench.py'),
+  r = subprocess.run([sys.executable, os.path.join(ROOT, 'tools', 'far', 'far_bench.py'),
                       '--help'], capture_output=True, text=True, timeout=120)
   assert r.returncode == 0, r.stderr[-1000:]
   assert 'far_lanes' in r.stdout and '--apps' in r.stdout
