@@ -600,7 +600,8 @@ std::vector<int> eligible_fused(const Planner* plan, const int64_t* dims) {
       continue;
     fused.push_back((int)k);
   }
-  std::sort(fused.begin(), fused.end(), [&](int a, int b) {
+  // (stable: same-depth alternatives keep the order of the table)
+  std::stable_sort(fused.begin(), fused.end(), [&](int a, int b) {
     return plan->kernels[a].depth > plan->kernels[b].depth;
   });
   return fused;
@@ -798,6 +799,10 @@ int fused_list(Planner* plan, Growth* g, const std::vector<int>& fused, const st
                std::vector<Launch>* list, int* max_depth_used, ScratchNeeds* needs) {
   const int m = (int)seq.size();
   int done = 0;
+  int iterate = 0, form = 0;
+  for (int k : seq) iterate += plan->kernels[k].depth;
+  const auto tuned_form = plan->tuned_form.find(split_key(plan, dims, iterate));
+  if (tuned_form != plan->tuned_form.end()) form = tuned_form->second;
   std::vector<Buffer> src = sweep_inputs(plan);
   for (int i = 0; i < m; ++i) {
     const soda_hip_kernel& desc = plan->kernels[seq[i]];
@@ -834,14 +839,35 @@ int fused_list(Planner* plan, Growth* g, const std::vector<int>& fused, const st
         const size_t n = strlen(plan->kernels[k].name), m = strlen(prefer);
         return n >= m && strcmp(plan->kernels[k].name + n - m, prefer) == 0;
       };
+      // (a price from the model and one from measured step times do not compare: a kernel
+      // without a calibration record never displaces one that has its own, and yields to it
+      // - 2-D: the 12-column-lane kernels `k<d>w` next to the shipped `k<d>`)
+      auto measured = [&](int k) {
+        return plan->kernels[k].step_ns_full > 0 && plan->kernels[k].step_ns_one > 0;
+      };
+      // (soda_hip_plan_tune timed the sweep by price, with the first and with the last
+      // kernel of every depth: Planner::tuned_form)
+      int first = -1, last = -1;
+      for (int k : fused)
+        if (plan->kernels[k].depth == desc.depth) {
+          if (first < 0) first = k;
+          last = k;
+        }
+      const int forced = form == 1 ? first : form == 2 ? last : -1;
       for (int k : fused) {
         if (k == seq[i] || plan->kernels[k].depth != desc.depth) continue;
         Launch other;
         bool other_empty;
-        if (make_launch(plan, k, a, &other, &other_empty) == 0 && !other_empty &&
-            other.est_us > 0 &&
-            (preferred(k) || (other.est_us < l.est_us && !preferred(l.kernel))))
-          l = other;
+        if (make_launch(plan, k, a, &other, &other_empty) != 0 || other_empty ||
+            other.est_us <= 0)
+          continue;
+        if (forced >= 0 && !prefer) {
+          if (k == forced) l = other;
+          continue;
+        }
+        const bool cheaper = measured(k) != measured(l.kernel) ? measured(k)
+                                                               : other.est_us < l.est_us;
+        if (preferred(k) || (cheaper && !preferred(l.kernel))) l = other;
       }
     }
     std::copy(tensor, tensor + SODA_HIP_MAX_TENSORS, l.buffer);

@@ -107,6 +107,11 @@ struct Planner {
   // index + box extents; the chunk choice uses it instead of the kernel's calibration
   // record (stream_chunk / stream_wgs_per_cu were measured on one box of one round)
   std::map<std::array<int64_t, 5>, std::array<int, 2>> tuned_stream;
+  // soda_hip_plan_tune, depths with several kernels (2-D `k24` / `k24w`, 3-D `k4` / `k4b`):
+  // how a sweep of these extents ran fastest, keyed like tuned_split - 0 or no entry: every
+  // launch takes the cheaper by price, 1: the table's first kernel of its depth that can
+  // run, 2: its last
+  std::map<std::array<int64_t, 5>, int> tuned_form;
 };
 
 // what follows stays inside libsoda_hip.so: the library exports its C ABI only

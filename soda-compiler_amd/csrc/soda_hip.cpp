@@ -584,8 +584,42 @@ int soda_hip_plan_tune(soda_hip_plan* plan, void* const* in, void* const* out,
     }
     return e;
   };
-  if (candidates.size() < 2) {      // one split only: the streaming launches remain
-    rc = tune_streaming(plan, dims, iterate, valid_lo, valid_hi, time_sweep);
+  // depths with several kernels in the blob (the run-time takes the cheaper by price per
+  // launch): the sweep by price, with the table's first and with its last kernel of every
+  // depth, one untimed run and the faster of two timed ones each - the fastest stays
+  // (Planner::tuned_form).  Only where the sweep has such a launch.
+  auto tune_forms = [&]() -> int {
+    std::vector<Launch> list;
+    int depth = 0;
+    ScratchNeeds needs;
+    int e = build_schedule(plan, dims, iterate, valid_lo, valid_hi, &list, &depth, &needs);
+    bool several = false;
+    for (const Launch& l : list) {
+      const soda_hip_kernel& kd = plan->kernels[l.kernel];
+      if (kd.kind != SODA_HIP_KERNEL_FUSED) continue;
+      for (size_t k = 0; k < plan->kernels.size(); ++k)
+        several = several || ((int)k != l.kernel && plan->kernels[k].depth == kd.depth &&
+                              plan->kernels[k].kind == SODA_HIP_KERNEL_FUSED);
+    }
+    if (e || !several) return e;
+    int best_form = 0;
+    float best_form_ms = 0;
+    for (int form = 0; form < 3 && !e; ++form) {
+      plan->tuned_form[key] = form;
+      float fastest = 0;
+      e = time_sweep(2, &fastest);
+      if (tuning_env("SODA_HIP_DEBUG"))
+        fprintf(stderr, "soda_hip: tune %d iteration(s): form %d -> %.1f us\n", iterate, form,
+                fastest * 1000.0);
+      if (form == 0 || fastest < best_form_ms) { best_form = form; best_form_ms = fastest; }
+    }
+    if (e) plan->tuned_form.erase(key);
+    else plan->tuned_form[key] = best_form;
+    return e;
+  };
+  if (candidates.size() < 2) {      // one split only: the forms and the streaming launches remain
+    rc = tune_forms();
+    if (!rc) rc = tune_streaming(plan, dims, iterate, valid_lo, valid_hi, time_sweep);
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     return rc;
@@ -607,6 +641,7 @@ int soda_hip_plan_tune(soda_hip_plan* plan, void* const* in, void* const* out,
   }
   if (rc) plan->tuned_split.erase(key);
   else plan->tuned_split[key] = candidates[best];
+  if (!rc) rc = tune_forms();
   if (!rc) rc = tune_streaming(plan, dims, iterate, valid_lo, valid_hi, time_sweep);
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);

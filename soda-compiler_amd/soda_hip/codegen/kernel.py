@@ -87,6 +87,17 @@ AUTO_WP_SQUEEZE_VGPRS = 152
 PACKED_DEEP_DEPTHS = (16, 20, 24)
 PACKED_DEEP_DEPTH = PACKED_DEEP_DEPTHS[0]
 PACKED_DEEP_WAVES_PER_EU = 3      # for the depths above 16
+# ... and at these depths a second kernel NEXT TO it, `<app>_fused_k<d>w`: lanes of 12 columns
+# as six pairs {c, c+6} (kernel_stream2d_wp.emit, cols=6), strips of 768 columns that keep
+# 720 at depth 24 (0.9375 against 464 of 512 = 0.906) and 32 instead of 2 x 22 instructions
+# per level-row of 12 cells; 256 registers = two workgroups per CU.  The run-time prices
+# both per launch (csrc/schedule.cpp: fused_list), as it does the two 3-D depth-4 forms.
+# Not depth 16: that kernel keeps four workgroups per CU at 128 registers.  Option
+# `wide12`: 0 = never, 1 = next to the shipped kernel, 2 = instead of it (tools).
+WIDE12_DEPTHS = (20, 24)
+WIDE12_OPTIONS = dict(cols=6, pairs=2, ring=AUTO_WP_RING, waves_per_eu=2, vgpr_budget=256,
+                      suffix='w')
+WIDE12_DEFAULT = 1
 # packable programs: the packed + ring form also replaces the single-wave form
 # from this depth on (jacobi2d 16384^2 per launch: depth 12 570 vs 617 us, depth 8
 # 501 vs 470 us - the single-wave form stays below)
@@ -190,6 +201,8 @@ FAR_MAX_PERIOD = 24
 # those both forms understand, and those only the wave-pipelined form has
 SHARED_2D_OPTIONS = ('skip_fill', 'vgpr_budget', 'max_period', 'align', 'waves_per_eu')
 WP_ONLY_OPTIONS = ('pairs', 'ring', 'split', 'prio', 'seam_probe')
+# ... and those that choose among the 2-D forms (stream2d_kernels) and reach no emit()
+SELECT_2D_OPTIONS = ('wide12',)
 
 HIPCC_FLAGS = ['-x', 'hip', '--offload-arch=gfx950', '--cuda-device-only',
                '--no-gpu-bundle-output', '-O3', '-ffp-contract=off',
@@ -451,10 +464,12 @@ FORM_OPTIONS = dict(
     fields3d=lambda k: k in FIELDS3D_OPTIONS,
     fields1d=lambda k: k in FIELDS1D_OPTIONS,
     stream1d=lambda k: k in STREAM1D_OPTIONS,
-    stream2d=lambda k: k not in WP_ONLY_OPTIONS + STREAM1D_OPTIONS and k != 'nt',
+    stream2d=lambda k: k not in WP_ONLY_OPTIONS + STREAM1D_OPTIONS + SELECT_2D_OPTIONS and
+    k != 'nt',
     stream2d_wp=lambda k: k in SHARED_2D_OPTIONS + WP_ONLY_OPTIONS,
     stream3d=lambda k: not k.startswith(('wp_', 'blk_')) and
-    k not in ('deep3d', 'deep3d_from', 'nontemporal') + STREAM1D_OPTIONS + LDS3D_OPTIONS,
+    k not in ('deep3d', 'deep3d_from', 'nontemporal') + STREAM1D_OPTIONS + LDS3D_OPTIONS +
+    SELECT_2D_OPTIONS,
     stream3d_lds=lambda k: k in LDS3D_OPTIONS)
 PREFIXED_FORMS = dict(stream3d_blk=('blk_', kernel_stream3d_blk.emit),
                       stream3d_wp=('wp_', kernel_stream3d_wp.emit))
@@ -808,8 +823,25 @@ def stream2d_piped(req, depth, strip, notes):
   return piped
 
 
+def stream2d_wide12(req, depth, strip, piped, notes):
+  """The 12-column-lane kernel of this depth next to (or instead of) the shipped wide packed
+  kernel `piped`, or None: only where the default selection chose that form in 16-byte lanes."""
+  how = int(req.options.get('wide12', WIDE12_DEFAULT))
+  if not how or depth not in WIDE12_DEPTHS or req.groups != -1 or req.cols or \
+      piped is None or piped[1].get('pairs') != 2 or piped[1]['cols'] != 4:
+    return None
+  options = dict(WIDE12_OPTIONS, **{k: v for k, v in form_options('stream2d_wp', req.options).items()
+                                    if k not in WIDE12_OPTIONS})
+  found, error = first_fusable(req.spec, depth, [
+      (kernel_stream2d_wp.emit, dict(dict(strip, groups=AUTO_WP_GROUPS), **options))])
+  if found is None:
+    notes.append('depth %d not in 12-column lanes: %s' % (depth, error))
+  return found
+
+
 def stream2d_kernels(req, notes):
-  """Single-array 2-D programs: per depth the wave-pipelined kernel, else the single-wave."""
+  """Single-array 2-D programs: per depth the wave-pipelined kernel, else the single-wave;
+  at WIDE12_DEPTHS the 12-column-lane kernel as a same-depth alternative."""
   spec = req.spec
   if spec['dim'] != 2 or kernel_stream2d.multi_field(spec) or req.rect:
     return
@@ -836,7 +868,13 @@ def stream2d_kernels(req, notes):
              dict(strip, **dict(far, **form_options('stream2d', req.options))))])
         if single is None:
           notes.append('depth %d not fused: %s' % (depth, error))
-    if piped is not None or single is not None:
+    # (the alternative first: whoever looks a depth up in the table finds the shipped kernel
+    # last; the run-time takes neither by its place)
+    wide12 = stream2d_wide12(req, depth, strip, piped, notes)
+    if wide12 is not None:
+      yield wide12
+    if (piped is not None or single is not None) and not (
+        wide12 is not None and int(req.options.get('wide12', WIDE12_DEFAULT)) == 2):
       yield piped if piped is not None else single
 
 

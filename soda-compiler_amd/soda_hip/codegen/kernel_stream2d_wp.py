@@ -163,7 +163,7 @@ def packable(spec):
 
 def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, groups=4,
          max_period=12, vgpr_budget=120, skip_fill=1, pairs=0, align='none',
-         ring=0, waves_per_eu=0, split=None, prio=None, seam_probe=0):
+         ring=0, waves_per_eu=0, split=None, prio=None, seam_probe=0, suffix=''):
   """Returns (text, kernel table entry).
 
   pairs=2 (needs the ring): ONE strip of 2 x 64 x C columns per wavefront; a
@@ -172,6 +172,17 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, groups=4,
   dppadd (the two operands per row that cross a half are two scalar adds, one of
   them DPP), but the x halo is paid once per 512 columns instead of per 256
   (jacobi2d depth 16: 480 of 512 columns kept against 448).
+
+  pairs=2 with cols=6 (`suffix` 'w': kernel.stream2d_wide12 builds it NEXT TO the cols=4 kernel
+  of depths 20 and 24): a lane holds 12 consecutive columns as six pairs {c, c+6}, a strip is
+  768 columns and keeps 720 at depth 24.  32 instructions per level-row of 12 cells (6 x 5
+  packed, 2 scalar seam adds) against 2 x 22 for 16: measured 6.2 % fewer VALU instructions
+  per launch.  A half (24 bytes) is no whole vector, so everything that moves a row goes by
+  the lane's three 16-byte pieces: the ring is [slot][piece][lane] and three
+  global_load_lds_dwordx4 per row fill it (one address, the piece in the immediate offset),
+  the hand-off rows hold three pieces per lane, a row is stored as three vectors with the
+  same ragged / full decision per piece.  216 window registers + the rest = 254 VGPRs, two
+  workgroups per CU (waves_per_eu=2), no scratch.  profiles/r18_wide12.txt.
 
   With pairs=1 the lane-crossing operands stay two scalars so that each shift folds
   into a scalar add (kernel_common: pk2_shifted; jacobi2d depth 16: 627 -> 610 us).
@@ -218,16 +229,21 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, groups=4,
   C = cols
   if pairs and not packable(spec):
     raise NotFusable('packed form: float programs of + - * / only')
-  if pairs and (C * elem) % 16:
-    raise NotFusable('packed form: whole 16-byte vectors per lane')
   P = 2 if pairs else 1
   wide = int(pairs) == 2
+  # wide lanes of 12 columns (C = 6 per half): a half is no whole 16-byte vector, the lane's
+  # 2C columns are three of them - the ring, the hand-off and the stores go by those pieces
+  wide12 = wide and C * elem == 24
+  if pairs and (C * elem) % 16 and not wide12:
+    raise NotFusable('packed form: whole 16-byte vectors per lane')
   if spec['dim'] != 2:
     raise NotFusable('2-D programs only')
   RS = int(ring)
   PF = RS - 2
-  if RS and (RS < 3 or C * elem != 16):
+  if RS and (RS < 3 or (C * elem != 16 and not wide12)):
     raise NotFusable('input ring: >= 3 slots, 16-byte lanes')
+  if wide12 and (not RS or seam_probe):
+    raise NotFusable('12-column lanes: through the input ring, no seam probe')
   if wide and not RS:
     raise NotFusable('wide strips come through the input ring')
   if isinstance(split, str):
@@ -240,6 +256,10 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, groups=4,
   if wide:      # the second half adds 64 x C columns, all of them output
     geo['w_out'] += LANES * C
   strip_cols = LANES * C * (2 if wide else 1)
+  if wide12:    # lanes start on 16-byte boundaries of the box's first line
+    geo['origin_align'] = 4
+  # the 16-byte pieces a lane's row is stored (and, 12-column lanes, loaded) in
+  NQ = 2 * C * elem // 16 if wide12 else P
   for inst in everything:
     for src, rel, _ in inst.reads:
       if abs(rel[0]) > C:
@@ -269,6 +289,10 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, groups=4,
   per_elem = max(1, elem // 4)
   est_vgprs = max(sum(i.keep for i in mine) for mine in per_wave) * C * per_elem * P + \
       4 * C * P + 20
+  if wide12:
+    # the windows, the row being computed, the three ring vectors it is assembled from
+    # (first wavefront) or the hand-off vectors, and addresses / counters
+    est_vgprs = max(sum(i.keep for i in mine) for mine in per_wave) * C * P + C * P + 12 + 16
   if est_vgprs > vgpr_budget:
     raise NotFusable('a wavefront would need about %d VGPRs (budget %d)'
                      % (est_vgprs, vgpr_budget))
@@ -285,7 +309,7 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, groups=4,
       below[id(src)] = max(below.get(id(src), -10**9), need - rel[1])
   for inst in everything:
     inst.first_step = max(0, inst.lag + geo['y_lo'] - below.get(id(inst), 0))
-  name = kernel_name(spec, depth)
+  name = kernel_name(spec, depth) + suffix
   L = final.lag
   T_in = builtin_type(in_type)
   T_out = builtin_type(types[out_name])
@@ -303,9 +327,10 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, groups=4,
           g, inst.ident, inst.lag, inst.keep,
           '-> HBM' if inst.final else inst.role))
   line('typedef %s %s __attribute__((ext_vector_type(%d), aligned(%d)));'
-       % (T_in, vec, C, elem))
-  line('typedef %s %s_lds __attribute__((ext_vector_type(%d), aligned(%d)));'
-       % (T_in, vec, C, C * elem))
+       % (T_in, vec, 4 if wide12 else C, elem))
+  if not wide12:
+    line('typedef %s %s_lds __attribute__((ext_vector_type(%d), aligned(%d)));'
+         % (T_in, vec, C, C * elem))
   if pairs:
     line('typedef float pk2 __attribute__((ext_vector_type(2)));')
   # LDS hand-off rows: 16-byte pieces, piece q of lane l at [q][l] (conflict-free)
@@ -335,7 +360,16 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, groups=4,
 
   def ring_issue(row_expr, slot_index):
     line('        { i64 row = %s; if (row > H - 1) row = H - 1;' % row_expr)
-    for h in range(P):
+    for q in range(NQ if wide12 else 0):
+      # piece q of every lane: [piece][lane] in LDS (the destination is one address per
+      # lane, 16 bytes apart), the lane's own columns 4q .. 4q+3 from memory.  The
+      # instruction's immediate offset moves BOTH addresses, so the three loads share one
+      # address computation and the LDS base takes the 16q bytes back
+      line('          __builtin_amdgcn_global_load_lds((const __attribute__(('
+           'address_space(1))) void*)(g_in + row * W + x), (__attribute__(('
+           'address_space(3))) void*)(&in_ring[%d][%d][0] - %d), 16, %d, 0);'
+           % (slot_index, q, 4 * q, 16 * q))
+    for h in range(0 if wide12 else P):
       line('          __builtin_amdgcn_global_load_lds((const __attribute__(('
            'address_space(1))) void*)(g_in + row * W + %s), (__attribute__(('
            'address_space(3))) void*)&in_ring[%d][%d][0], 16, 0, %d);'
@@ -343,8 +377,19 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, groups=4,
               ('xb' if h else 'x'), slot_index, h, 0))
     line('        }')
 
+  # 12-column lanes: where piece q of a lane's row starts, and its four values (column k of
+  # the lane is the low half of pair k below C, the high half of pair k - C from there on)
+  piece_x = ['x'] + ['xq%d' % q for q in range(1, NQ)]
+
+  def piece_value(q, j):
+    k = 4 * q + j
+    return 'out_row[%d][%d]' % (k % C, k // C)
+
+  def piece_values(q):
+    return ''.join(' v[%d] = %s;' % (j, piece_value(q, j)) for j in range(4))
+
   def emit_body(mine, guarded):
-    probed = [i for i in mine if i.role in ('compute', 'lds_out') or i.final] if seam_probe \
+    probed =[i for i in mine if i.role in ('compute', 'lds_out') or i.final] if seam_probe \
         else []
     for u in range(period):
       line('      {  // unrolled step %d' % u)
@@ -354,7 +399,30 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, groups=4,
           ring_issue('head + %d' % (u + PF), (u + PF) % RS)
           # row head+u was issued PF rows ago
           line('        __builtin_amdgcn_s_waitcnt(%d);  // vmcnt(%d)'
-               % (vmcnt(PF * P), PF * P))
+               % (vmcnt(PF * NQ), PF * NQ))
+          if wide12:
+            # twelve ds_read_b32 straight into the halves of the six pairs {c, c+6}, off ONE
+            # address register (slot, piece and column are immediate offsets): no register
+            # move and no address arithmetic; invisible to the compiler like
+            # soda_lds_read_f4, for the same reason.  A lane stride of 16 bytes puts the 64
+            # lanes of a read on 8 banks; the conflict-free alternative, three ds_read_b128
+            # and twelve moves that pick the pairs out, was measured and removed (12 VALU
+            # instructions per row on the busiest wavefront: per depth-24 launch at
+            # 16384^2 767.2 against 759.0 us, at 8192^2 224.0 against 221.0,
+            # profiles/r18_wide12.txt)
+            row_bytes = NQ * LANES * 16
+            names = ['f%d' % k for k in range(2 * C)]
+            line('        { float %s;' % ', '.join(names))
+            line('          asm volatile("%s\\n\\ts_waitcnt lgkmcnt(0)" : %s : "v"(ring_rd) : '
+                 '"memory");' % (
+                     '\\n\\t'.join('ds_read_b32 %%%d, %%%d offset:%d' % (
+                         k, 2 * C, (u % RS) * row_bytes + (k // 4) * LANES * 16 + (k % 4) * 4)
+                                   for k in range(2 * C)),
+                     ', '.join('"=&v"(%s)' % n for n in names)))
+            for c in range(C):
+              line('          %s[%d][%d] = pk2{f%d, f%d};' % (inst.ident, s, c, c, c + C))
+            line('        }')
+            continue
           if wide and C == 4:
             # the four pairs straight from the LDS read (ds_read2_b32) instead of
             # two ds_read_b128 and eight register moves: 0.4-0.7 % per depth-16
@@ -457,14 +525,25 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, groups=4,
           # common case, decided once per strip: no lane's vector straddles an
           # edge of the store range, so a lane stores its whole vector or nothing
           line('            if (!ragged) {')
-          for half in range(P):
+          for q in range(NQ if wide12 else 0):
+            line('              if (full_%d) { %s v;%s *(%s*)(g_out + y * W + %s) = v; }'
+                 % (q, vec, piece_values(q), vec, piece_x[q]))
+          for half in range(0 if wide12 else P):
             sel = '[%d]' % half if pairs else ''
             xv = 'xb' if half else 'x'
             line('              if (full_%d) { %s v;%s *(%s*)(g_out + y * W + %s) = v; }'
                  % (half, vec, ''.join(' v[%d] = out_row[%d]%s;' % (c, c, sel)
                                        for c in range(C)), vec, xv))
           line('            } else {')
-          for half in range(P):
+          for q in range(NQ if wide12 else 0):
+            xv = piece_x[q]
+            line('            { %s* q = g_out + y * W + %s;' % (T_out, xv))
+            line('            if (%s >= st_lo && %s + 4 <= st_hi) { %s v;%s *(%s*)q = v; }'
+                 % (xv, xv, vec, piece_values(q), vec))
+            line('            else {%s } }' % ''.join(
+                ' if (%s + %d >= st_lo && %s + %d < st_hi) q[%d] = %s;'
+                % (xv, j, xv, j, j, piece_value(q, j)) for j in range(4)))
+          for half in range(0 if wide12 else P):
             sel = '[%d]' % half if pairs else ''
             sfx = 'b' if half and not wide else ''
             xv = 'xb' if half else 'x'
@@ -488,7 +567,7 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, groups=4,
   line('DEV void %s_strip(const soda_hip_args& a, const i64 xs, const i64 x, '
        'const i64 xb, const i64 y0, const i64 y1, const int wave, const int lane,'
        % name)
-  ring_dims = (P, LANES * C) if RS else (1, 1)
+  ring_dims = (NQ, LANES * 4) if wide12 else (P, LANES * C) if RS else (1, 1)
   if pairs and seam_probe:
     line('    float (*handoff)[2][%d][%d][%d], %s (*in_ring)[%d][%d], float* seam_lds) {'
          % (S, pieces, LANES * 4, T_in, ring_dims[0], ring_dims[1]))
@@ -514,7 +593,19 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, groups=4,
   line('  (void)g_in; (void)g_out; (void)st_lo; (void)st_hi; (void)W; (void)H; '
        '(void)xb; (void)in_ring;')
   parts = []
-  for half in range(P):
+  if wide12:
+    line('  const i64 %s; %s' % (
+        ', '.join('xq%d = x + %d' % (q, 4 * q) for q in range(1, NQ)),
+        ' '.join('(void)xq%d;' % q for q in range(1, NQ))))
+    # where this lane's piece 0 of ring slot 0 lies in LDS (only the first wavefront reads)
+    line('  const unsigned ring_rd = (unsigned)(unsigned long long)&in_ring[0][0][0] + '
+         'lane * 16u; (void)ring_rd;')
+    for q in range(NQ):
+      xv = piece_x[q]
+      line('  const bool full_%d = %s >= st_lo && %s + 4 <= st_hi; (void)full_%d;'
+           % (q, xv, xv, q))
+      parts.append('(!full_%d && %s + 4 > st_lo && %s < st_hi)' % (q, xv, xv))
+  for half in range(0 if wide12 else P):
     sfx = 'b' if half and pairs and not wide else ''
     xv = 'xb' if half else 'x'
     line('  const bool full_%d = %s >= st_lo%s && %s + %d <= st_hi%s; (void)full_%d;'
