@@ -35,6 +35,8 @@ The unit holds
       1-D, x-neighbours beyond the next lane (FIRs of more than 9 float taps, double
                         stencils of radius 3 and up): kernel_stream1d / kernel_fields1d with
                         chained wave shifts, only with `far_taps=True`;
+      3-D, 8- and 16-bit integer volumes, depth 1-2: kernel_stream3d_pk (kernel_stream3d with
+                        packed windows), only with `packed_cells=True`;
   * `soda_hip_meta`, JSON describing the program and the kernel table, which
     libsoda_hip.so reads back from the loaded blob.
 
@@ -56,7 +58,8 @@ import tempfile
 from .. import __version__
 from . import (kernel_common, kernel_fields1d, kernel_fields2d, kernel_fields3d, kernel_stage,
                kernel_stream1d, kernel_stream2d, kernel_stream2d_wp, kernel_stream3d,
-               kernel_stream3d_blk, kernel_stream3d_lds, kernel_stream3d_wp)
+               kernel_stream3d_blk, kernel_stream3d_lds, kernel_stream3d_pk,
+               kernel_stream3d_wp)
 from . import spec as specmod
 from . import switches
 
@@ -196,6 +199,16 @@ LDS3D_OPTIONS = ('lds_shape',)
 # to MAX_HOPS lanes away and windows of up to this many rows (a radius-8 window keeps 17 rows
 # and the 3 in flight; the row loop is unrolled by the period)
 FAR_MAX_PERIOD = 24
+
+# the packed-cell 3-D form (kernel_stream3d_pk; `packed_cells`): depths of an iteration chain,
+# capped by the program's `iterate`, and the options its emit() receives (`cols` and `rows`
+# fix the tile shape, `waves_per_eu` / `vgpr_budget` the occupancy level, instead of the first
+# that fits).  The rule of the 1-D and far forms: a depth that does not beat the per-stage
+# schedule by more than the spread leaves the list.  Both do (profiles/r19_packed3d.txt, 512^3 /
+# 256^3 x 4: the slowest against per stage, castvol3d depth 1 at 256^3, 0.302 against 0.309 ms
+# at a spread of 0.004; smooth3d depth 2 0.744 against 1.194 ms at 512^3)
+PACKED3D_DEPTHS = (1, 2)
+PACKED3D_OPTIONS = ('rows', 'vgpr_budget', 'max_period', 'waves_per_eu', 'nt', 'chunk_planes')
 
 # generator options of the fused 2-D forms that `generate` passes through:
 # those both forms understand, and those only the wave-pipelined form has
@@ -470,7 +483,8 @@ FORM_OPTIONS = dict(
     stream3d=lambda k: not k.startswith(('wp_', 'blk_')) and
     k not in ('deep3d', 'deep3d_from', 'nontemporal') + STREAM1D_OPTIONS + LDS3D_OPTIONS +
     SELECT_2D_OPTIONS,
-    stream3d_lds=lambda k: k in LDS3D_OPTIONS)
+    stream3d_lds=lambda k: k in LDS3D_OPTIONS,
+    stream3d_pk=lambda k: k in PACKED3D_OPTIONS)
 PREFIXED_FORMS = dict(stream3d_blk=('blk_', kernel_stream3d_blk.emit),
                       stream3d_wp=('wp_', kernel_stream3d_wp.emit))
 
@@ -502,7 +516,7 @@ class Request:
     # the opt-in forms asked for ({keyword: bool}, codegen/switches.py), what each LDS-plane
     # form did ({key of soda_hip_meta: note}, lds3d_kernels), and the table entries made so
     # far: an LDS-plane form is emitted only where they hold no fused depth-1 kernel
-    self.on = {s.keyword: bool(on[s.keyword]) for s in switches.SWITCHES}
+    self.on = {s.keyword: bool(on[s.keyword]) for s in switches.ALL}
     self.meta_notes, self.made = {}, []
     # what a far-reach switch adds to the arguments of its dimensionality's forms (FAR_FORMS;
     # generate()): the switches concern programs of different dimensionality, so one dict
@@ -997,6 +1011,57 @@ def deep3d_kernels(req, notes):
       yield found
 
 
+def packed3d_kernels(req, notes):
+  """3-D programs over 8- and 16-bit integer volumes, when generate() was asked for packed
+  cells: kernel_stream3d_pk at depth 1, and at depth 2 for an iteration chain, in the tile
+  shape that keeps most of the tile among those the register budget takes.  What the switch
+  did goes into req.meta_notes, not into `notes`: apart from the metadata, the text of a
+  program outside the class is the same with and without the switch."""
+  if not req.on['packed_cells']:
+    return
+  spec = req.spec
+  key = switches.BY_KEYWORD['packed_cells'].note
+  types = specmod.tensor_c_types(spec)
+  ends = [t['c_type'] for t in spec['inputs']] + [types[o] for o in spec['outputs']]
+  if all(specmod.ELEM_SIZE[t] >= 4 for t in ends):
+    req.meta_notes[key] = 'not concerned: 4- or 8-byte elements'
+    return
+  why = kernel_stream3d_pk.class_refusal(spec)
+  if why:
+    req.meta_notes[key] = 'not fused: %s' % why
+    return
+  chain = req.single_array and ends[0] == ends[-1]
+  wanted = [d for d in PACKED3D_DEPTHS if d <= max(1, spec['iterate'])] if chain else [1]
+  if req.depths is not None and chain:
+    wanted = sorted(set([1] + [d for d in req.depths if d in PACKED3D_DEPTHS]))
+  refusals = []
+
+  def attempts(depth):
+    options = form_options('stream3d_pk', req.options)
+    shapes = [s for s in kernel_stream3d_pk.shapes_by_kept_fraction(spec, depth)
+              if not req.cols or s[1] == req.cols]
+    if 'rows' in options:
+      shapes = [(options.pop('rows'), req.cols or shapes[0][1])]
+    # stores around the caches for boxes beyond the Infinity Cache, as kernel_stream3d's
+    options.setdefault('nt', 4)
+    # most waves per SIMD first, then most of the tile kept (kernel_stream3d_pk.TILE_SHAPES
+    # has the measurements); an occupancy or a budget given as an option is the only level
+    levels = kernel_stream3d_pk.OCCUPANCY_LEVELS
+    if 'waves_per_eu' in options or 'vgpr_budget' in options:
+      levels = [(options.get('waves_per_eu', 2), options.get('vgpr_budget', 240))]
+    return [(kernel_stream3d_pk.emit, dict(options, rows=rows, cols=lane_cols,
+                                           waves_per_eu=waves, vgpr_budget=budget))
+            for waves, budget in levels for rows, lane_cols in shapes]
+  # (the cost figures of annotate_cost are the single-wave 3-D form's model: no calibration
+  # key exists for these kernels, their price is unmeasured)
+  made = None
+  for found in fused_at_depths(req, refusals, wanted, attempts):
+    made = made or found[1]['name']
+    yield found
+  req.meta_notes[key] = made or 'not fused: %s' % refusals[0][len('depth 1 not fused: '):]
+  notes.extend(n for n in refusals if made)
+
+
 # The LDS-plane forms (kernel_stream3d_lds), one per switch.  `fields`: the form over
 # several outputs - for the plane ring, which takes one output or several, a function of the
 # request.  `ring`: several planes of an input in LDS.  `refusals`: in the order they are
@@ -1051,7 +1116,7 @@ def lds3d_kernels(form, req, notes):
 # the kernel families in the order their kernels enter the table; each yields the
 # (text, entry) of the kernels it selects for this request and appends to `notes`
 FAMILIES = (fields2d_kernels, fields3d_kernels, fields1d_kernels, stream1d_kernels,
-            stream2d_kernels, stream3d_kernels, deep3d_kernels,
+            stream2d_kernels, stream3d_kernels, deep3d_kernels, packed3d_kernels,
             functools.partial(lds3d_kernels, LDS_PLANES),
             functools.partial(lds3d_kernels, LDS_FIELDS),
             functools.partial(lds3d_kernels, LDS_RING))
@@ -1060,7 +1125,7 @@ FAMILIES = (fields2d_kernels, fields3d_kernels, fields1d_kernels, stream1d_kerne
 def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
              fused=True, depths=None, inline=True, wave_groups=None,
              fuse_outputs=False, lds_planes=False, lds_fields=False, far_lanes=False,
-             lds_ring=False, far_taps=False, **fused_options):
+             lds_ring=False, far_taps=False, packed_cells=False, **fused_options):
   """Returns (kernel text, kernel table).  `depths` overrides the default set
   of fused depths (depth 1 is always included: the scheduler needs it).
   `fuse_outputs`: a one-pass 2-D / 3-D program with several outputs that is not
@@ -1102,8 +1167,13 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   kernel_stream1d.MAX_HOPS_1D lanes), at the family's usual depths and under the usual names
   `<app>_fused_k<d>`; like every fused 1-D kernel they are launched under a depth limit
   (switches.depth_limit_of).  Every other program keeps its table and, apart from the entry
-  `far_taps` of soda_hip_meta, its text."""
-  given = locals()      # every row of switches.SWITCHES is a parameter above: read by keyword
+  `far_taps` of soda_hip_meta, its text.
+  `packed_cells`: a 3-D program with one output whose inputs and output are integers of one
+  width, 1 or 2 bytes (locals of 1, 2 or 4 bytes), gets kernel_stream3d's kernels with packed
+  windows (kernel_stream3d_pk) under the usual names `<app>_fused_k1` and, for an iteration
+  chain, `_k2`, in the default schedule.  Every other program keeps its table and, apart
+  from the entry `packed_cells` of soda_hip_meta, its text."""
+  given = locals()      # every row of switches.ALL is a parameter above: read by keyword
   # kernels are generated from the LOWERED program (pointwise-only locals folded
   # into their readers); the blob is still identified by the source program
   source = spec
@@ -1119,7 +1189,7 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   parts.append(text)
   notes = []
   req = Request(spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
-                fused_options, {s.keyword: given[s.keyword] for s in switches.SWITCHES})
+                fused_options, {s.keyword: given[s.keyword] for s in switches.ALL})
   for form in FAR_FORMS:
     req.far.update(far_arguments(form, req))
   for family in FAMILIES if fused else ():

@@ -3,7 +3,9 @@
 A switch is a boolean keyword of generate() that adds one kernel form to the programs in its
 class.  Everything outside the generator that has to know a switch - the command line, the
 generated hosts, the run-time's depth limit, the name of the prebuilt code object - reads it
-here: an opt-in form more is a row more.  Data and pure functions only.  (The far-reach
+here: an opt-in form more is a row more - of SWITCHES, the forms for windows and outputs the
+default forms refuse, or of ELEMENT_SWITCHES, the forms by element width; readers take ALL.
+Data and pure functions only.  (The far-reach
 switches' depth limit depends on the program: depth_limit_of reads it off kernel.FAR_FORMS,
 where such a form is a row as well.)
 """
@@ -49,7 +51,18 @@ SWITCHES = (
            'with one to three outputs (launched under a depth limit of 1: '
            'soda_hip_plan_set_max_depth)', '.ldsr', True, 'lds_ring'),
 )
-BY_KEYWORD = {s.keyword: s for s in SWITCHES}
+# ... and the forms that differ by ELEMENT WIDTH, not by window or outputs: a table of their
+# own with the same columns.  Everything that reads the switches reads ALL, both tables in this
+# order; a further form by element width is a row more here.
+ELEMENT_SWITCHES = (
+    Switch('packed_cells', '--hip-packed-cells', 'hip_packed_cells',
+           'the fused 3-D kernels for a program over 8- or 16-bit integer volumes (one '
+           'output, inputs and output of one width): one tile per wavefront with the '
+           'windows kept packed, four or two cells per register, at depths 1 and 2; they '
+           'run in the default schedule', '.pk', False, 'packed_cells'),
+)
+ALL = SWITCHES + ELEMENT_SWITCHES
+BY_KEYWORD = {s.keyword: s for s in ALL}
 
 
 def given(on):
@@ -58,12 +71,13 @@ def given(on):
   for name in on:
     if name not in BY_KEYWORD:
       raise TypeError("got an unexpected keyword argument '%s'" % name)
-  return [s for s in SWITCHES if on.get(s.keyword)]
+  return [s for s in ALL if on.get(s.keyword)]
 
 
-def from_args(args):
-  """{keyword: bool} of every switch, read from an argparse namespace."""
-  return {s.keyword: bool(getattr(args, s.dest, False)) for s in SWITCHES}
+def from_args(args, rows=SWITCHES):
+  """{keyword: bool} of every switch of `rows` (the command line reads ALL), read from an
+  argparse namespace."""
+  return {s.keyword: bool(getattr(args, s.dest, False)) for s in rows}
 
 
 def depth_limit_flags(on):
