@@ -44,9 +44,38 @@ OCCUPANCY_LEVELS = ((4, 128), (3, 168), (2, 240))
 # what a lane holds besides its windows: addresses in flight, the cells and dwords of the row
 # in the making, the dwords that crossed lanes (read off the compiler's resource reports under
 # the occupancy attribute: 8 x 4 tiles 64 registers for 48 of windows and 120 for 96, 8 x 8
-# uint8 tiles 75 for 64)
-def overhead_vgprs(rows, cols, dwords):
-  return 2 * rows + cols + dwords + 8
+# uint8 tiles 75 for 64).  Those reports were of rows with no more crossing registers than
+# the lane's own dwords.  A stage that reads several rows or tensors across the lane's edge
+# crosses more (`crossings`, the count row_crossings() takes from the reads), and each such
+# register costs about four: the shifted copy, what is extracted from it, and the same for
+# the rows the compiler makes side by side - capped at two per cell of the row.  (Two int16
+# inputs and a uint8 local in 8-column lanes, 8 crossing registers in the local's rows: 80
+# registers of windows, 139 in all with no ceiling, 159 with a trivial output stage, 125
+# with the same operands and no x offset.  36 on top of the windows made it a four-waves
+# kernel that spilled 29 registers to scratch; 52 make it a three-waves kernel.)
+def overhead_vgprs(rows, cols, dwords, crossings=0):
+  beyond = min(4 * max(0, crossings - dwords), 2 * cols)
+  return 2 * rows + cols + dwords + beyond + 8
+
+
+def row_crossings(insts, cols):
+  """The most registers of the two neighbour lanes that a row of `cols` cells of one stage
+  reads: the wave shifts emit() hoists per row."""
+  crossings = 0
+  for inst in insts:
+    if inst.stage is None:
+      continue
+    crossed = set()
+    for src, rel, _ in inst.reads:
+      per = 4 // specmod.ELEM_SIZE[src.c_type] if specmod.ELEM_SIZE[src.c_type] < 4 else 1
+      for c in range(cols):
+        j = c + rel[0]
+        if j < 0 or j >= cols:
+          crossed.add((src.ident, rel[1], rel[2], j < 0, (j % cols) // per))
+    crossings = max(crossings, len(crossed))
+  return crossings
+
+
 _UNSIGNED = {1: 'unsigned char', 2: 'unsigned short'}
 
 
@@ -149,7 +178,7 @@ def emit(spec, depth, cols=8, rows=8, chunk_planes=64, prefetch=0, max_period=12
   period = rotation_period(insts, max_period)
   # dwords, not cells
   est_vgprs = sum(inst.keep * R * regs_per_row(inst.c_type, C) for inst in insts) + \
-      overhead_vgprs(R, C, DW)
+      overhead_vgprs(R, C, DW, row_crossings(insts, C))
   if est_vgprs > vgpr_budget:
     raise NotFusable('depth %d would need about %d VGPRs in %d x %d tiles (budget %d)'
                      % (depth, est_vgprs, R, C, vgpr_budget))

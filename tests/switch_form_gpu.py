@@ -161,6 +161,19 @@ def shapes_of(form, k, spec, iterate):
           (mz + 29, 3 * ty + 5 + my, 2 * tx + 37 + mx)]
 
 
+def volume_shapes_of(k, margins):
+  """shapes_of for the 3-D entry `k` of a program that may reach nowhere along z (fill_rows 0:
+  no z offset at all; 1: one-sided), `margins` (x, y, z) as Form.margins gives them: the same
+  four shapes, the second with the fewest planes that leave the box one - below the fill
+  where there is one to stay below."""
+  mx, my, mz = margins
+  tx, ty = k['tile'][:2]
+  return [(mz + 1, my + 1, mx + 1),
+          (mz + max(1, k['fill_rows'] - 1), ty + 1 + my, tx + 1 + mx),
+          (mz + 2 * SHORTEST_CHUNK - 1, my + 3, mx + 5),
+          (mz + 29, 3 * ty + 5 + my, 2 * tx + 37 + mx)]
+
+
 def wide_shape_of(form, k, spec, iterate):
   """The shape of the full-width-operand run: one tile and an odd remainder."""
   if spec['dim'] == 2:
