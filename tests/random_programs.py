@@ -298,6 +298,50 @@ def program_set(n_plain=40, n_deep=16, n_ops=16, n_struct=16, n_cube=12):
 NARROW_ENDS = ('uint8', 'int8', 'uint16', 'int16')
 
 
+def integer_term(rng, read, small, names, first, nonzero=False):
+  """One term of an integer stage over operator_program's operators, shared by
+  narrow_volume_program and line_program: `read(name, nonzero=...)` gives an integer operand
+  that loads tensor `name`, `small(name)` says whether that operand may be multiplied by a
+  thousand without leaving an int.  (`&&` and `||` under a product: the reference prints
+  their parentheses away, and at the top of a sum they would swallow it.)"""
+  def literal():
+    return str(rng.choice(['1', '2', '3', '5', '7', '0x0f', '0x3', '017', '3u', '6l',
+                           '0xffu', '9']))
+  other = names[int(rng.integers(0, len(names)))]
+  a = read(first, nonzero=nonzero)
+  r = rng.random()
+  if r < 0.10:
+    return '(%s %% %s)' % (a, str(rng.choice(['3', '5', '7', '0x10'])))
+  if r < 0.20:
+    return '(%s & %s)' % (a, literal())
+  if r < 0.28:
+    return '(%s | %s)' % (a, read(other))
+  if r < 0.36:
+    return '(%s ^ %s)' % (a, read(other))
+  if r < 0.46:
+    return '(%s %s %s)' % (a, str(rng.choice(['<', '<=', '>', '>=', '==', '!='])),
+                           read(other))
+  if r < 0.52:
+    return '2 * (%s > %s && %s != %s)' % (a, literal(), read(first), literal())
+  if r < 0.58:
+    return '3 * (%s < %s || %s == %s)' % (a, literal(), read(other), literal())
+  if r < 0.64:
+    return '(-%s)' % a
+  if r < 0.70:
+    return '(~%s & 0xff)' % a
+  if r < 0.74:
+    return '(!%s)' % a
+  if r < 0.80:
+    cast = str(rng.choice(['int32', 'uint16', 'int16', 'uint8', 'int8'][not small(first):]))
+    return '%s(%s) * %s' % (cast, a, literal())
+  if r < 0.86:
+    return '%s / %s' % (a, str(rng.choice(['2', '3', '4'])))
+  if r < 0.93 and small(first):        # leaves 16 bits, then comes back
+    return '(%s * %s) / %s' % (a, str(rng.choice(['300', '1000', '257'])),
+                               str(rng.choice(['7', '13', '11'])))
+  return '(%s - %s) / %s' % (a, read(other), str(rng.choice(['3', '5', '2'])))
+
+
 def narrow_volume_program(rng, seed):
   """3-D programs of the packed-cell kernels' class (kernel.generate's `packed_cells`): one
   output, 1 or 2 inputs, all ends 8-bit or all 16-bit (the output, or the second input, now
@@ -379,44 +423,8 @@ def narrow_volume_program(rng, seed):
     # values within 17 bits: what may be multiplied (an int32 local may hold 1e8)
     return types[name] != 'int32' or types['.stage'] == 'int32'
 
-  def literal():
-    return str(rng.choice(['1', '2', '3', '5', '7', '0x0f', '0x3', '017', '3u', '6l',
-                           '0xffu', '9']))
-
   def term(names, first, nonzero=False):
-    other = names[int(rng.integers(0, len(names)))]
-    a = read(first, nonzero=nonzero)
-    r = rng.random()
-    if r < 0.10:
-      return '(%s %% %s)' % (a, str(rng.choice(['3', '5', '7', '0x10'])))
-    if r < 0.20:
-      return '(%s & %s)' % (a, literal())
-    if r < 0.28:
-      return '(%s | %s)' % (a, read(other))
-    if r < 0.36:
-      return '(%s ^ %s)' % (a, read(other))
-    if r < 0.46:
-      return '(%s %s %s)' % (a, str(rng.choice(['<', '<=', '>', '>=', '==', '!='])),
-                             read(other))
-    if r < 0.52:
-      return '2 * (%s > %s && %s != %s)' % (a, literal(), read(first), literal())
-    if r < 0.58:
-      return '3 * (%s < %s || %s == %s)' % (a, literal(), read(other), literal())
-    if r < 0.64:
-      return '(-%s)' % a
-    if r < 0.70:
-      return '(~%s & 0xff)' % a
-    if r < 0.74:
-      return '(!%s)' % a
-    if r < 0.80:
-      cast = str(rng.choice(['int32', 'uint16', 'int16', 'uint8', 'int8'][not small(first):]))
-      return '%s(%s) * %s' % (cast, a, literal())
-    if r < 0.86:
-      return '%s / %s' % (a, str(rng.choice(['2', '3', '4'])))
-    if r < 0.93 and small(first):        # leaves 16 bits, then comes back
-      return '(%s * %s) / %s' % (a, str(rng.choice(['300', '1000', '257'])),
-                                 str(rng.choice(['7', '13', '11'])))
-    return '(%s - %s) / %s' % (a, read(other), str(rng.choice(['3', '5', '2'])))
+    return integer_term(rng, read, small, names, first, nonzero)
 
   def integer_expression(names, must):
     parts = [] if negative_only else [read(names[int(rng.integers(0, len(names)))],
@@ -545,6 +553,256 @@ def write_narrow_volume_set(path):
     json.dump(programs, f, indent=1, sort_keys=True)
 
 
+LINE_ENDS = ('uint16', 'int16', 'int32', 'uint32', 'float', 'int64', 'double')
+LINE_SIZE = dict(uint16=2, int16=2, int32=4, uint32=4, float=4, int64=8, double=8)
+# the other type of the same width a local may have: the signedness flip, int32 for float and
+# float for int32, int64 <-> double
+LINE_OTHER = dict(uint16='int16', int16='uint16', uint32='int32', int32='float', float='int32',
+                  int64='double', double='int64')
+# bytes of a lane per element size (default_cols follows `burst width`, 8 bits a byte): 16, 8
+# and, for 4- and 8-byte elements, one cell
+LINE_LANES = {2: (16, 8), 4: (16, 8, 4), 8: (16, 8)}
+LINE_MAX_HOPS = 8                        # kernel_stream1d.MAX_HOPS_1D
+# lanes away of the far programs, in the set's order; the first 8 is the program with 8 lanes
+# on either side
+LINE_HOPS = (2, 3, 8, 4, 5, 2, 6, 8, 3, 7, 4, 2, 8, 3, 5, 2, 4, 6, 3, 7, 2, 8)
+LINE_MODES = ('both', 'lo', 'both', 'hi', 'both')
+# iteration counts beyond 5: the depth-8 and depth-12 kernels; ln10 is a far program whose
+# table stops at depth 2
+LINE_DEEP = {3: 13, 12: 8, 21: 12, 10: 9}
+# what a stage reads of a 4- / 8-byte integer tensor away from its store point: the low 16 bits
+# or the quotient by this
+LINE_REDUCE = {4: 16384, 8: 1048576}
+LINE_TO_FLOAT = {4: 65536, 8: 1048576}   # the quotient a float stage converts
+
+
+def line_program(rng, seed):
+  """1-D programs of the fused 1-D kernels' class (kernel_stream1d; with reads beyond the
+  neighbour lane, kernel.generate's `far_taps`): one input, one output of its type - the types
+  of LINE_ENDS in turn -, 0 to 2 locals of the end type or of the other type of its width
+  (LINE_OTHER).  `burst width` gives lanes of 16 or 8 bytes or of one 4- or 8-byte cell, C
+  cells.  A third of the programs (seed % 3 == 0) stays within the neighbour lane; the others
+  read up to `hops` lanes away (LINE_HOPS, 2 to 8), with offsets of exactly +-hops C and of
+  +-((hops - 1) C + 1) placed on purpose - on a local where the program has one -, the offsets
+  around a dword's width for 16-bit cells, and the rest anywhere in the span.  The axis is
+  two-sided, lo-only or hi-only per program (LINE_MODES); seed % 8 == 7: negative offsets
+  only.  `iterate` 1 to 5, 8 to 13 for LINE_DEEP.
+
+  Integer stages are sums of integer_term's terms, float stages weighted sums with weights of
+  at most 1 in sum.  What is restricted, and why - all of it because plain C++ has no defined
+  answer otherwise, none of it for a kernel's sake:
+    * a 4- or 8-byte integer tensor is an operand as its low 16 bits, as its quotient by
+      LINE_REDUCE, or - at the store point - as its half: a stage's terms then stay below a
+      quarter of the type's range whatever the tensor holds, and with the half of the store
+      point below the range itself, at any iteration count (8 terms of at most 2^18 * 255, and 2^30, stay
+      below 2^31; 8 of 2^45 * 255, and 2^62, below 2^63);
+    * a float stage reads such a tensor as float(quotient by LINE_TO_FLOAT), so float values
+      stay within 2^16 (2^43 for double) where the inputs do, and int32(f * s), s <= 4, the
+      only way from float to integer, is in range - on the fixtures' inputs and on
+      gpu_util.wide_inputs' 2^13 alike;
+    * nothing divides by a tensor;
+    * no operand and no sum starts with `(` where its last operand ends with `)`: the
+      reference prints a chain of operands as `(` + text + `)` after taking every leading `(`
+      and trailing `)` off the text, whether they match or not.  A comparison of
+      `(a(3) / 16384)` with `int16(a(1))` so loses its parentheses to the sum around it, which
+      then yields 0 or 1 in every cell; a sum from `((x * 257) / 11)` to `(3 * (...))` comes
+      out unbalanced, which no compiler takes.  So the quotient goes under a cast, and a sum
+      starts with a read.
+  Every stage reads the store point of a parent, so every window contains it and the
+  reference's loops have an answer - except in the negative-only programs.  The output reads
+  everything still unused away from the store point: no stage is dead.
+  Returns (text, end type, iterate, far)."""
+  end = LINE_ENDS[seed % 7]
+  size = LINE_SIZE[end]
+  floaty_end = end in ('float', 'double')
+  lanes = LINE_LANES[size]
+  lane_bytes = lanes[(seed // 7 + seed % 7) % len(lanes)]
+  cols = lane_bytes // size
+  negative_only = seed % 8 == 7
+  far = seed % 3 != 0
+  far_index = seed - seed // 3 - 1
+  hops = LINE_HOPS[far_index % len(LINE_HOPS)] if far else 1
+  mode = LINE_MODES[seed % 5]
+  eight_a_side = far and far_index == 2
+  if eight_a_side:
+    mode = 'both'
+  reach = hops * cols
+  span = {'both': (-reach, reach), 'lo': (-reach, 0), 'hi': (0, reach)}[mode]
+  if negative_only:
+    span = (-reach, -1)
+  n_locals = (1, 2, 0)[far_index % 3] if far else int(rng.integers(0, 3))
+  iterate = LINE_DEEP.get(seed, int(rng.integers(1, 6)))
+  if eight_a_side:
+    iterate = 5                          # depth 4 leaves no cell of a segment
+  if negative_only:
+    iterate = min(iterate, 3)
+  # offsets placed on purpose, first the lane `hops` away itself or the first cell that needs
+  # it (in turn), on either side the span has
+  edge = reach if far_index % 2 == 0 or eight_a_side else (hops - 1) * cols + 1
+  placed = [v for v in (edge, -edge, -reach if edge != reach else -(reach - cols + 1))
+            if span[0] <= v <= span[1]] if far else []
+  types = {'a': end}
+
+  def x_offset():
+    lo, hi = span
+    r = rng.random()
+    if r < 0.25:
+      pool = [-reach, reach]             # the same cell of the lane `hops` away
+    elif r < 0.45:
+      pool = [-(reach - cols + 1), reach - cols + 1]     # the first cell that needs it
+    elif r < 0.6 and size == 2:
+      pool = [-3, -2, 2, 3]              # past the dword, either side
+    elif r < 0.8:
+      pool = [int(rng.integers(lo, hi + 1))]
+    else:
+      pool = [-2, -1, 0, 1, 2]
+    pool = [v for v in pool if lo <= v <= hi] or [lo if lo else hi]
+    return int(rng.choice(pool))
+
+  def offset(name, nonzero=False):
+    if nonzero and placed and (name != 'a' or n_locals == 0):
+      return placed.pop(0)
+    while True:
+      at = x_offset()
+      if at or not nonzero:
+        return at
+
+  def read(name, centre=False, nonzero=False):
+    """A read as an integer operand."""
+    at = 0 if centre else offset(name, nonzero)
+    text = '%s(%d)' % (name, at)
+    t = types[name]
+    if t in ('float', 'double'):
+      scale = str(rng.choice(['1.0', '2.0', '4.0'])) + ('f' if t == 'float' else '')
+      return '%s(%s * %s)' % ('int32' if t == 'float' else 'int64', text, scale)
+    if LINE_SIZE[t] == 2:
+      return text
+    if centre:
+      return '%s / 2' % text
+    if rng.random() < 0.5:
+      return 'int16(%s)' % text
+    # (under a cast: an operand that starts with `(` would cost the term around it its own
+    # parentheses, see below)
+    return 'int%d(%s / %d)' % (8 * LINE_SIZE[t], text, LINE_REDUCE[LINE_SIZE[t]])
+
+  def term(names, first, nonzero=False):
+    return integer_term(rng, read, lambda name: True, names, first, nonzero)
+
+  def pick(names):
+    return names[int(rng.integers(0, len(names)))]
+
+  def again(must):
+    """Further reads of the last tensor of `must` that offset() places: as many as it takes
+    for every offset placed on purpose to be read."""
+    takers = [n for n in must if n != 'a' or n_locals == 0]
+    return [takers[-1]] * max(0, len(placed) - len(takers)) if takers else []
+
+  def integer_expression(names, must):
+    # the sum starts with a plain operand - the store point, or in the negative-only programs
+    # a read as it is - and not with a term in parentheses
+    parts = [read(pick(names), nonzero=True) if negative_only else
+             read(pick(names), centre=True)]
+    parts += [term(names, n, nonzero=True) for n in must + again(must)]
+    parts += [term(names, pick(names)) for _ in range(int(rng.integers(1, 3)))]
+    text = parts[0]
+    for t in parts[1:]:
+      text += str(rng.choice([' + ', ' - ', ' + '])) + t
+    return text
+
+  def float_expression(names, must, c_type):
+    suffix = 'f' if c_type == 'float' else ''
+    weights = ['0.25', '0.25', '0.125', '0.125', '0.125', '0.0625']
+
+    def operand(name, at):
+      text = '%s(%d)' % (name, at)
+      t = types[name]
+      if t in ('float', 'double'):
+        return text
+      return '%s(%s / %d)' % (c_type, text, LINE_TO_FLOAT[LINE_SIZE[t]])
+    reads = [(n, True) for n in must + again(must)]
+    reads += [(pick(names), False) for _ in range(int(rng.integers(1, 3)))]
+    ats = [(n, offset(n, nonzero)) for n, nonzero in reads]
+    if not negative_only:                # the store point of a parent
+      ats.insert(0, (pick(names), 0))
+    parts = ['%s * %s%s' % (operand(n, at), weights[i], suffix)
+             for i, (n, at) in enumerate(ats[:len(weights)])]
+    text = parts[0]
+    for t in parts[1:]:
+      text += str(rng.choice([' + ', ' - '])) + t
+    return text
+
+  def expression(c_type, names, must):
+    if c_type in ('float', 'double'):
+      return float_expression(names, must, c_type)
+    return integer_expression(names, must)
+
+  lines = ['kernel: ln%d' % seed, 'burst width: %d' % (8 * lane_bytes), 'unroll factor: 1',
+           'iterate: %d' % iterate, 'input %s: a(*)' % end]
+  names, unused = ['a'], ['a']
+  for k in range(n_locals):
+    name = 'loc%d' % k
+    t = LINE_OTHER[end] if rng.random() < 0.6 else end
+    must = [unused.pop(0)] if rng.random() < 0.7 else []
+    lines.append('local %s: %s(0) = %s' % (t, name, expression(t, names, must)))
+    types[name] = t
+    names.append(name)
+    unused.append(name)
+  lines.append('output %s: out(0) = %s' % (end, expression(end, names, unused)))
+  assert not placed, (seed, placed)
+  return '\n'.join(lines) + '\n', end, iterate, far
+
+
+def line_set(n=32):
+  """[(key, text, dim, iterate, generate()'s keywords)] - the programs of
+  tests/test_gpu_random1d.py: `far_taps` for those that read beyond the neighbour lane, and
+  for a few of the set other segments per wavefront than the default four."""
+  out = []
+  for seed in range(n):
+    if seed in LINE_SLOW:
+      continue
+    rng = np.random.default_rng(31000 + seed)
+    text, end, iterate, far = line_program(rng, seed)
+    keywords = dict(far_taps=True) if far else {}
+    if seed % 8 == 2:
+      keywords['segs'] = 2
+    if seed % 16 == 5:
+      keywords['segs'] = 8
+    out.append(('ln%d' % seed, text, 1, iterate, keywords))
+  return out
+
+
+# seeds left out of the set because their case took too long on an MI355X: none.  The two
+# cases above three times the set's median, ln3 and ln21 at 1.6 and 1.5 s, are the programs
+# with a depth-12 kernel, which the set has to hold (profiles/r20_random1d.txt)
+LINE_SLOW = ()
+LINE_SEAM_MARGIN = 40      # cells a fixture is longer than the widest segment's and the box's
+
+
+def write_line_set(path):
+  """tests/golden/random1d_programs.json: text, iterate and generate()'s keywords per program,
+  and the length of its reference fixture - the cells the widest segment of its table stores,
+  plus what the box of all iterations is shorter than the array, plus 40: a segment seam of
+  every kernel of the table lies inside the box.  Needs the package."""
+  import json
+  import os
+  import sys
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  sys.path.insert(0, os.path.join(root, 'soda-compiler_amd'))
+  from soda_hip import frontend
+  from soda_hip.codegen import kernel
+  from soda_hip.codegen import spec as specmod
+  programs = {}
+  for key, text, dim, iterate, keywords in line_set():
+    spec = specmod.spec_from_stencil(frontend.loads(text))
+    _, table = kernel.generate(spec, **keywords)
+    widest = max(k['w_out'] for k in table if k['kind'] == 'fused')
+    lo, hi = specmod.iteration_margins(specmod.inline_pointwise(spec), iterate)[-1]
+    programs[key] = dict(text=text, dim=dim, iterate=iterate, generate=keywords,
+                         grid=[widest + lo[0] + hi[0] + LINE_SEAM_MARGIN])
+  with open(path, 'w') as f:
+    json.dump(programs, f, indent=1, sort_keys=True)
+
+
 if __name__ == '__main__':      # writes the program texts the fixtures are made from
   import json
   import os
@@ -552,6 +810,9 @@ if __name__ == '__main__':      # writes the program texts the fixtures are made
   here = os.path.dirname(os.path.abspath(__file__))
   if sys.argv[1:] == ['--narrow-volumes']:
     write_narrow_volume_set(os.path.join(here, 'golden', 'packed3d_random_programs.json'))
+    sys.exit(0)
+  if sys.argv[1:] == ['--lines']:
+    write_line_set(os.path.join(here, 'golden', 'random1d_programs.json'))
     sys.exit(0)
   with open(os.path.join(here, 'golden', 'random_programs.json'), 'w') as f:
     json.dump({k: dict(text=t, dim=d, iterate=i) for k, t, d, i in program_set()},

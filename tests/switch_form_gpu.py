@@ -1,6 +1,7 @@
 """What the GPU tests of the opt-in kernel forms share (tests/test_gpu_lds3d.py,
 test_gpu_lds3d_fields.py, test_gpu_lds3d_ring.py, test_gpu_far2d.py): one record per form
-says what differs, the functions here run it.  Everything goes through the C ABI from the
+says what differs, the functions here run it; and the lengths and splits of the 1-D forms'
+tests (test_gpu_far1d.py, test_gpu_random1d.py).  Everything goes through the C ABI from the
 prebuilt `<app><suffix>.hsaco` of the form's switch; every comparison is of bytes."""
 import collections
 import json
@@ -172,6 +173,32 @@ def volume_shapes_of(k, margins):
           (mz + max(1, k['fill_rows'] - 1), ty + 1 + my, tx + 1 + mx),
           (mz + 2 * SHORTEST_CHUNK - 1, my + 3, mx + 5),
           (mz + 29, 3 * ty + 5 + my, 2 * tx + 37 + mx)]
+
+
+def line_lengths(k, m):
+  """Array lengths from the constants of the fused 1-D entry `k`, m = cells the launch's box
+  is shorter than the array: a box of one cell, of half a segment, of one segment and of one
+  cell more, of one workgroup tile less and plus one cell, and three tiles and 17 cells."""
+  w_out, tile = k['w_out'], k['tile'][0]
+  assert tile == 4 * k['segs'] * w_out
+  return [m + 1, m + w_out // 2, m + w_out, m + w_out + 1, m + tile - 1, m + tile + 1,
+          3 * tile + 17]
+
+
+def splits_of(depths, iterate):
+  """`iterate` as launches of the table's depths under every limit, deepest first and
+  shallowest first.  (The depths need not be consecutive: a table may lack one that leaves a
+  segment no cell, and the shallower ones fill what it would have taken.)"""
+  out = []
+  for limit in depths:
+    s = []
+    for d in sorted(depths, reverse=True):
+      while d <= limit and sum(s) + d <= iterate:
+        s.append(d)
+    for split in (s, s[::-1]):
+      if split not in out:
+        out.append(split)
+  return out
 
 
 def wide_shape_of(form, k, spec, iterate):

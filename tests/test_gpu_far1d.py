@@ -88,30 +88,13 @@ def opened(app):
 
 
 def lengths(k, spec, iterate):
-  """Array lengths from the entry's own constants, m = cells the launch's box of `iterate`
-  iterations is shorter than the array: a box of one cell, of half a segment, of one segment
-  and of one cell more, of one workgroup tile less and plus one cell, and three tiles and 17
-  cells."""
+  """harness.line_lengths, m = cells the launch's box of `iterate` iterations is shorter than
+  the array."""
   (m,) = FORM.margins(spec, iterate)
-  w_out, tile = k['w_out'], k['tile'][0]
-  assert tile == 4 * k['segs'] * w_out
-  return [m + 1, m + w_out // 2, m + w_out, m + w_out + 1, m + tile - 1, m + tile + 1,
-          3 * tile + 17]
+  return harness.line_lengths(k, m)
 
 
-def splits_of(depths, iterate):
-  """`iterate` as launches of the table's depths under every limit, deepest first and
-  shallowest first."""
-  out = []
-  for limit in depths:
-    s = []
-    for d in sorted(depths, reverse=True):
-      while d <= limit and sum(s) + d <= iterate:
-        s.append(d)
-    for split in (s, s[::-1]):
-      if split not in out:
-        out.append(split)
-  return out
+splits_of = harness.splits_of
 
 
 def check_length(prog, orc, n, iterate, splits):
