@@ -57,7 +57,7 @@ def add_arguments(parser):
                       'by burst width)')
   parser.add_argument('--hip-chunk-rows', type=int, dest='hip_chunk_rows',
                       metavar='ROWS', help='outer-dimension rows per workgroup')
-  for switch in switches.ALL:
+  for switch in switches.EVERY:
     parser.add_argument(switch.flag, action='store_true', dest=switch.dest,
                         help=switch.help)
 
@@ -102,7 +102,7 @@ def print_code(stencil, args):
   spec = to_spec(stencil)
   warn_ignored_overrides(args)
   max_depth = getattr(args, 'hip_max_depth', None)
-  on = switches.from_args(args, switches.ALL)
+  on = switches.from_args(args, switches.EVERY)
   files = dict(kernel=getattr(args, 'hip_kernel_file', None),
                host=getattr(args, 'hip_host_file', None),
                header=getattr(args, 'hip_header_file', None),

@@ -94,8 +94,9 @@ def print_selfcheck(spec, out):
   w('        box_hi[s][d] = std::max(box_hi[s][d], 0);\n')
   w('      }\n    }\n')
   for j, n in enumerate(ins):
-    if len(ins) == len(outs):
-      # output j of the previous iteration feeds input j (core.py:342-360)
+    if len(ins) == len(outs) and types[n] == types[outs[j]]:
+      # output j of the previous iteration feeds input j (core.py:342-360); an output of
+      # another type than its input feeds nothing back: such a program runs one iteration
       w('    const %s* %s_img = it == 0 ? (const %s*)inputs[%d] : (((it - 1) & 1) ? '
         'buf_%s_1 : buf_%s_0);\n' % (types[n], n, types[n], j, outs[j], outs[j]))
     else:

@@ -37,6 +37,10 @@ The unit holds
                         chained wave shifts, only with `far_taps=True`;
       3-D, 8- and 16-bit integer volumes, depth 1-2: kernel_stream3d_pk (kernel_stream3d with
                         packed windows), only with `packed_cells=True`;
+      2-D, one output, inputs and output of different element widths (8- or 16-bit pixels
+                        filtered in float, float quantised to integers): kernel_stream2d at
+                        depth 1 with every tensor's loads and stores in its own width, only
+                        with `mixed_widths=True`;
   * `soda_hip_meta`, JSON describing the program and the kernel table, which
     libsoda_hip.so reads back from the loaded blob.
 
@@ -209,6 +213,67 @@ FAR_MAX_PERIOD = 24
 # at a spread of 0.004; smooth3d depth 2 0.744 against 1.194 ms at 512^3)
 PACKED3D_DEPTHS = (1, 2)
 PACKED3D_OPTIONS = ('rows', 'vgpr_budget', 'max_period', 'waves_per_eu', 'nt', 'chunk_planes')
+
+# the mixed-width 2-D form (kernel_stream2d with `mixed`; `mixed_widths`): a lane holds C
+# consecutive cells of every tensor, so C decides how many bytes of each it moves.  The shapes
+# run from the one in which the WIDEST end fills a lane's 16 bytes (C = 16 / widest: uint8 next
+# to float then moves 4 bytes per lane) to the one in which the NARROWEST does (C = 16 /
+# narrowest: the float side then moves 64 bytes per lane in four pieces and costs C registers
+# per retained row), every power of two between them.  mixed_shapes() gives them in the order
+# they are tried; a shape the register estimate refuses is skipped; `cols=` is the only shape.
+# MIXED_WIDEST_FIRST: the order that won the measurement (profiles/r21_mixed2d.txt).
+MIXED_WIDEST_FIRST = True
+
+
+def mixed_end_sizes(spec):
+  """Element sizes of the inputs and of the outputs, in that order."""
+  types = specmod.tensor_c_types(spec)
+  return [specmod.ELEM_SIZE[t['c_type']] for t in spec['inputs']] + \
+      [specmod.ELEM_SIZE[types[o]] for o in spec['outputs']]
+
+
+def mixed_shapes(spec, cols=None):
+  """Columns per lane of the mixed-width form, in the order they are tried."""
+  if cols:
+    return [cols]
+  sizes = mixed_end_sizes(spec)
+  shapes = [c for c in (1, 2, 4, 8, 16) if 16 // max(sizes) <= c <= 16 // min(sizes)]
+  return shapes if MIXED_WIDEST_FIRST else shapes[::-1]
+
+
+def mixed_arguments(req):
+  """What `mixed_widths` adds to kernel_stream2d.emit's arguments for this request:
+  dict(mixed=True) for a 2-D program with one output whose inputs and output differ in
+  element width, {} for every other program, whose text then stays what it is.  Leaves in
+  req.meta_notes why a program is not in the class; mixed_note() says the rest."""
+  spec = req.spec
+  if not req.on['mixed_widths']:
+    return {}
+  key = switches.BY_KEYWORD['mixed_widths'].note
+  types = specmod.tensor_c_types(spec)
+  if len(set(mixed_end_sizes(spec))) == 1:
+    req.meta_notes[key] = 'not concerned: inputs and output of one width'
+  elif spec['dim'] != 2:
+    req.meta_notes[key] = 'not fused: the mixed-width form handles 2-D programs'
+  elif len(spec['outputs']) != 1:
+    req.meta_notes[key] = 'not fused: the mixed-width form handles programs with one output'
+  elif '_Float16' in [t['c_type'] for t in spec['inputs']] + [types[spec['outputs'][0]]]:
+    req.meta_notes[key] = 'not fused: the mixed-width form does not take half elements'
+  else:
+    return dict(mixed=True)
+  return {}
+
+
+def mixed_note(req, notes):
+  """The switch's entry of soda_hip_meta for a program in its class: the kernel made, or
+  why there is none."""
+  if not req.mixed:
+    return
+  made = [e['name'] for e in req.made if e['kind'] == 'fused' and e['depth'] == 1]
+  why = [n[len('depth 1 not fused: '):] for n in notes if n.startswith('depth 1 not fused: ')]
+  req.meta_notes[switches.BY_KEYWORD['mixed_widths'].note] = made[0] if made else \
+      'not fused: %s' % (why + ['no 2-D form takes it'])[0]
+
 
 # generator options of the fused 2-D forms that `generate` passes through:
 # those both forms understand, and those only the wave-pipelined form has
@@ -435,6 +500,11 @@ def annotate_cost(entry, spec):
     cells_out = entry['tile'][0] * entry['tile'][1]
   entry['step_valu'] = int(valu)
   entry['step_bytes'] = int((n_in * cells_in + n_out * cells_out) * elem)
+  sizes = mixed_end_sizes(spec)
+  if len(set(sizes)) > 1 and spec['dim'] == 2 and entry.get('kind') == 'fused' and \
+      n_out == 1 and 'groups' not in entry:
+    # inputs and output of different widths (kernel_stream2d, `mixed`): summed per tensor
+    entry['step_bytes'] = int(cells_in * sum(sizes[:n_in]) + cells_out * sizes[-1])
   # measured step times of exactly this kernel, when it has been calibrated
   # (soda_hip_kernel.step_ns_full / step_ns_one / stream_gbps)
   measured = calibration().get(calibration_key(entry, spec))
@@ -478,7 +548,7 @@ FORM_OPTIONS = dict(
     fields1d=lambda k: k in FIELDS1D_OPTIONS,
     stream1d=lambda k: k in STREAM1D_OPTIONS,
     stream2d=lambda k: k not in WP_ONLY_OPTIONS + STREAM1D_OPTIONS + SELECT_2D_OPTIONS and
-    k != 'nt',
+    k not in ('nt', 'mixed'),       # (`mixed`: set by the switch `mixed_widths` alone)
     stream2d_wp=lambda k: k in SHARED_2D_OPTIONS + WP_ONLY_OPTIONS,
     stream3d=lambda k: not k.startswith(('wp_', 'blk_')) and
     k not in ('deep3d', 'deep3d_from', 'nontemporal') + STREAM1D_OPTIONS + LDS3D_OPTIONS +
@@ -516,11 +586,13 @@ class Request:
     # the opt-in forms asked for ({keyword: bool}, codegen/switches.py), what each LDS-plane
     # form did ({key of soda_hip_meta: note}, lds3d_kernels), and the table entries made so
     # far: an LDS-plane form is emitted only where they hold no fused depth-1 kernel
-    self.on = {s.keyword: bool(on[s.keyword]) for s in switches.ALL}
+    self.on = {s.keyword: bool(on[s.keyword]) for s in switches.EVERY}
     self.meta_notes, self.made = {}, []
     # what a far-reach switch adds to the arguments of its dimensionality's forms (FAR_FORMS;
     # generate()): the switches concern programs of different dimensionality, so one dict
     self.far = {}
+    # ... and what `mixed_widths` adds for a program in its class (mixed_arguments)
+    self.mixed = {}
     # one-pass programs with several outputs get the fields forms at depth 1 (opt-in:
     # profiles/r12_rect.txt); such a program is in nobody else's class
     fuse_outputs = self.on['fuse_outputs']
@@ -749,21 +821,33 @@ def stream2d_single(req, depth, strip, notes, far):
   # the memory-bound depths store around the caches when a launch's box
   # does not fit the Infinity Cache (kernel_stream2d.emit: nontemporal)
   options = dict({'nontemporal': 4} if depth <= NT_AUTO_MAX_DEPTH_2D else {},
-                 **dict(far, **form_options('stream2d', req.options)))
+                 **dict(far, **dict(req.mixed, **form_options('stream2d', req.options))))
   # ... and where no STAGE is read across lanes (depth 1 of the samples) their
   # strips do not overlap at all (align='exact': whole 128-byte lines in and
   # out, the seam columns from one extra vector load per row and side)
   aligns = ['exact', 'full'] if strip.get('align') == 'full' else \
       [options.pop('align', None) or strip['align']]
+  if req.mixed and len(aligns) > 1:
+    # a narrow lane shape of this class may keep no whole line of its narrowest tensor
+    # (kernel_stream2d.geometry refuses): then strips as wide as the halo allows
+    aligns.append('none')
   attempts = []
-  for how in aligns:
-    shape = dict(strip, align=how)
-    if how == 'exact' and req.prefetch is None:
-      # six rows in flight per wavefront (two workgroups per CU on the arrays
-      # that matter, soda_hip_kernel.stream_wgs_per_cu)
-      shape['prefetch'] = EXACT_PREFETCH
-    attempts.append((kernel_stream2d.emit, dict(shape, **options)))
+  # (the mixed-width class: every lane shape of mixed_shapes in turn, each as aligned as it
+  # can be; every other program has the one shape of `strip`)
+  for lane_cols in mixed_shapes(req.spec, req.cols) if req.mixed else [strip['cols']]:
+    for how in aligns:
+      shape = dict(strip, align=how, cols=lane_cols)
+      if how == 'exact' and req.prefetch is None:
+        # six rows in flight per wavefront (two workgroups per CU on the arrays
+        # that matter, soda_hip_kernel.stream_wgs_per_cu)
+        shape['prefetch'] = EXACT_PREFETCH
+      attempts.append((kernel_stream2d.emit, dict(shape, **options)))
   single, error = first_fusable(req.spec, depth, attempts)
+  if single is None and req.mixed:
+    # (the note names the refusal of the FIRST lane shape, the one the program would ship in,
+    # in its last alignment - not that of the last shape tried, which is mostly the register
+    # estimate's for the widest lanes)
+    _, error = first_fusable(req.spec, depth, attempts[:len(aligns)])
   if single is None:
     notes.append('depth %d not fused: %s' % (depth, error))
   return single
@@ -1125,7 +1209,8 @@ FAMILIES = (fields2d_kernels, fields3d_kernels, fields1d_kernels, stream1d_kerne
 def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
              fused=True, depths=None, inline=True, wave_groups=None,
              fuse_outputs=False, lds_planes=False, lds_fields=False, far_lanes=False,
-             lds_ring=False, far_taps=False, packed_cells=False, **fused_options):
+             lds_ring=False, far_taps=False, packed_cells=False, mixed_widths=False,
+             **fused_options):
   """Returns (kernel text, kernel table).  `depths` overrides the default set
   of fused depths (depth 1 is always included: the scheduler needs it).
   `fuse_outputs`: a one-pass 2-D / 3-D program with several outputs that is not
@@ -1172,8 +1257,17 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   width, 1 or 2 bytes (locals of 1, 2 or 4 bytes), gets kernel_stream3d's kernels with packed
   windows (kernel_stream3d_pk) under the usual names `<app>_fused_k1` and, for an iteration
   chain, `_k2`, in the default schedule.  Every other program keeps its table and, apart
-  from the entry `packed_cells` of soda_hip_meta, its text."""
-  given = locals()      # every row of switches.ALL is a parameter above: read by keyword
+  from the entry `packed_cells` of soda_hip_meta, its text.
+  `mixed_widths`: a 2-D program with one output where some input's element size differs from
+  another input's or from the output's (sizes of 1, 2, 4 or 8 bytes, no `half`; uint8 pixels
+  to float, float and a uint8 map to uint16), which kernel_stream2d refuses with `inputs and
+  output of different widths`, gets ONE kernel `<app>_fused_k1` of that form with every
+  tensor's loads and stores in its own width, in the default schedule; depth 1 only, since
+  the DSL iterates between equal types.  The lane shape is the first of mixed_shapes() the
+  register estimate takes, or `cols`.  Not together with `far_lanes`: a program in the class
+  that reads beyond the neighbour lane keeps its per-stage kernels.  Every other program
+  keeps its table and, apart from the entry `mixed_widths` of soda_hip_meta, its text."""
+  given = locals()      # every row of switches.EVERY is a parameter above: read by keyword
   # kernels are generated from the LOWERED program (pointwise-only locals folded
   # into their readers); the blob is still identified by the source program
   source = spec
@@ -1189,9 +1283,10 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
   parts.append(text)
   notes = []
   req = Request(spec, max_depth, cols, chunk_rows, prefetch, depths, wave_groups,
-                fused_options, {s.keyword: given[s.keyword] for s in switches.ALL})
+                fused_options, {s.keyword: given[s.keyword] for s in switches.EVERY})
   for form in FAR_FORMS:
     req.far.update(far_arguments(form, req))
+  req.mixed = mixed_arguments(req)
   for family in FAMILIES if fused else ():
     for ftext, entry in family(req, notes):
       parts.append(ftext)
@@ -1199,6 +1294,7 @@ def generate(spec, max_depth=None, cols=None, chunk_rows=None, prefetch=None,
       req.made.append(entry)
   for form in FAR_FORMS:
     far_note(form, req, notes)
+  mixed_note(req, notes)
   if notes:
     parts.append(''.join('// %s\n' % n for n in notes))
   extra = dict(program_hash=kernel_common.program_hash(source),

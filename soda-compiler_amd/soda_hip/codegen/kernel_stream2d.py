@@ -130,8 +130,12 @@ def build_pipeline(spec, depth, prefetch, fields=False):
   return insts, final
 
 
-def geometry(spec, depth, cols, chunk_rows, align='none'):
+def geometry(spec, depth, cols, chunk_rows, align='none', line_elem=None):
   """Strip/chunk geometry for `depth` fused iterations.
+
+  line_elem: the element size a 128-byte line is counted in - input 0's, or for a program
+  whose inputs and output differ in width (emit, `mixed`) the NARROWEST of them: a column
+  that lies on a line of the narrowest tensor lies on a line of every wider one.
 
   align: 'none'  - strips as wide as the halo allows;
          'store' - every strip's OUTPUT columns start and end on a 128-byte line
@@ -154,7 +158,7 @@ def geometry(spec, depth, cols, chunk_rows, align='none'):
     lo, hi = margins[-1]     # the hull over all fields, composed over `depth` iterations
   else:
     lo, hi = margins[0]
-  elem = specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
+  elem = line_elem or specmod.ELEM_SIZE[spec['inputs'][0]['c_type']]
   line = max(cols, 128 // elem)
   line -= line % cols
   halo_lo = -(-lo[0] // cols) * cols      # padded up to whole vectors
@@ -163,6 +167,9 @@ def geometry(spec, depth, cols, chunk_rows, align='none'):
     halo_lo = -(-lo[0] // line) * line
   if align == 'exact':
     halo_lo = halo_hi = 0
+    if line_elem and LANES * cols % line:
+      raise NotFusable('seam-free strips: %d columns are no whole 128-byte lines of every '
+                       'tensor' % (LANES * cols))
   w_out = LANES * cols - halo_lo - halo_hi
   origin_align = cols
   if align == 'exact':
@@ -173,6 +180,10 @@ def geometry(spec, depth, cols, chunk_rows, align='none'):
     origin_align = line
   elif align not in ('none', 'store', 'full', 'exact'):
     raise ValueError('align: %r' % (align,))
+  elif line_elem and align != 'none':
+    # (a lane shape too narrow for it: the caller falls back to the next alignment)
+    raise NotFusable('aligned strips: %d columns keep no whole 128-byte line of every tensor'
+                     % (LANES * cols))
   if w_out < cols:
     raise NotFusable('depth %d leaves no output columns in a strip' % depth)
   return dict(x_lo=lo[0], x_hi=hi[0], y_lo=lo[1], y_hi=hi[1],
@@ -234,10 +245,23 @@ def check_reach(readers, cols, hops, max_hops=MAX_HOPS):
         raise NotFusable('x offset %d exceeds the %d columns a lane holds' % (dx, cols))
 
 
-def estimated_vgprs(insts, cols):
+def estimated_vgprs(insts, cols, mixed=False):
   """Every retained row costs `cols` VGPRs per lane (2 x for 8-byte types), the edge
   columns of seam-free strips along with them; past ~224 the kernel drops below two
-  waves per SIMD and then spills."""
+  waves per SIMD and then spills.
+  mixed: the program's inputs and output differ in width (emit): every row counts by its own
+  type - a loaded row stays the vector it arrived as (emit: `packed`), cols * size bytes in
+  whole registers - and what a step keeps besides by the widest: the row being put together,
+  its store vector and the cells of narrow rows unpacked for their readers.  The factor 9 is
+  FITTED to what the compiler allots (hipcc 7.2, gfx950) over the samples at every lane shape,
+  the closest being edge8f at 16 columns, 184 VGPRs against 216, and quant2d at 8, 192 against
+  196; tests/test_mixed2d_codegen.py holds every shipped kernel to its estimate."""
+  if mixed:
+    words = lambda inst: max(1, specmod.ELEM_SIZE[inst.c_type] // 4)
+    rows = sum(inst.keep * (-(-cols * specmod.ELEM_SIZE[inst.c_type] // 4)
+                            if inst.stage is None else cols * words(inst)) +
+               inst.keep * sum(inst.edges.values()) * words(inst) for inst in insts)
+    return rows + 9 * cols * max(words(inst) for inst in insts) + 16
   return sum(inst.keep * (cols + sum(getattr(inst, 'edges', {}).values())) *
              max(1, specmod.ELEM_SIZE[inst.c_type] // 4) for inst in insts) + \
       4 * cols + 16 + far_vgprs(insts, cols)
@@ -317,12 +341,18 @@ def kernel_name(spec, depth):
 
 def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=DEFAULT_MAX_PERIOD,
          vgpr_budget=244, waves_per_eu=0, skip_fill=1, nontemporal=0, align='none',
-         steady=None, stage_edges=0, stream_wgs=None, hops=1):
+         steady=None, stage_edges=0, stream_wgs=None, hops=1, mixed=False):
   """Returns (text, kernel table entry) for one fused depth.
 
   hops: how many lanes away an x-neighbour may lie (1 .. MAX_HOPS; lane_operand chains one
   wave shift per lane).  Strips, halo lanes and store ranges follow geometry() whatever the
   reach; only the seam-free strips (align='exact') are written for the neighbour lane.
+
+  mixed: take a program whose inputs and output differ in element width (kernel.generate's
+  `mixed_widths`; depth 1: the DSL iterates between equal types only).  A lane holds `cols`
+  consecutive cells of EVERY tensor, so its loads and its store are vectors of different
+  byte widths: every input through a vector of its own type, the store in 16-byte pieces
+  where the lane's output row is longer.  Without it such a program is refused as ever.
 
   steady (default: on for depth <= 2, the memory-bound kernels): the rows of a chunk
   whose loads need no clamping and whose results are all stored run in a loop of their
@@ -339,13 +369,24 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=DEFAULT_
   in_type = spec['inputs'][0]['c_type']
   out_name = spec['outputs'][0]
   elem = specmod.ELEM_SIZE[in_type]
-  if any(specmod.ELEM_SIZE[t['c_type']] != elem for t in spec['inputs']) or \
-      specmod.ELEM_SIZE[types[out_name]] != elem:
+  # the element sizes of the memory ends: of the first input (every input's, outside the
+  # mixed-width class), of the output, and the narrowest and widest of them all
+  out_elem = specmod.ELEM_SIZE[types[out_name]]
+  end_sizes = [specmod.ELEM_SIZE[t['c_type']] for t in spec['inputs']] + [out_elem]
+  mixed = bool(mixed) and len(set(end_sizes)) > 1
+  if len(set(end_sizes)) > 1 and not mixed:
     raise NotFusable('inputs and output of different widths')
+  if mixed:
+    if '_Float16' in [t['c_type'] for t in spec['inputs']] + [types[out_name]]:
+      raise NotFusable('mixed widths: half elements')
+    if depth != 1:
+      raise NotFusable('mixed widths: depth 1 only')
+    if hops != 1:
+      raise NotFusable('mixed widths: a read beyond the neighbour lane')
   if cols is None:
-    cols = max(1, 16 // elem)
+    cols = max(1, 16 // max(end_sizes))
   insts, final = build_pipeline(spec, depth, prefetch)
-  geo = geometry(spec, depth, cols, chunk_rows, align)
+  geo = geometry(spec, depth, cols, chunk_rows, align, min(end_sizes) if mixed else None)
   C = cols
   check_reach(insts, cols, hops)
   exact = align == 'exact'
@@ -354,7 +395,9 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=DEFAULT_
   # the steady-state loop without any branch (round 4): the row's store is a raw buffer
   # store whose lane offset is out of range in lanes that store nothing (halo lanes of
   # overlapping strips), a scheduling fence per row, loaded rows kept packed - see emit_body
-  flat = steady and C * elem in (4, 8, 16)
+  # (a lane's output row of more than 16 bytes - the mixed-width class - leaves in 16-byte
+  # pieces; one below 4 bytes keeps the guarded store)
+  flat = steady and C * out_elem in ((4, 8, 16, 32, 64, 128) if mixed else (4, 8, 16))
   for inst in insts:
     inst.edges = dict(lo=0, hi=0)    # columns beyond the strip that readers ask for, per side
   if exact:
@@ -380,7 +423,7 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=DEFAULT_
           for side in ('lo', 'hi'):
             src.edges[side] = max(src.edges[side], inst.edges[side])
   period = rotation_period(insts, max_period)
-  est_vgprs = estimated_vgprs(insts, cols)
+  est_vgprs = estimated_vgprs(insts, cols, mixed)
   if est_vgprs > vgpr_budget:
     raise NotFusable('depth %d would need about %d VGPRs (budget %d)'
                      % (depth, est_vgprs, vgpr_budget))
@@ -393,9 +436,9 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=DEFAULT_
   # 64-bit lane mask in a pair of SGPRs across it: more pairs than the SGPR file has left,
   # so the compiler parked 16 to 56 SGPRs in VGPR lanes.  As in kernel_fields2d the per-lane
   # operand goes through an empty asm there, and the conditions are recomputed where used.
-  lean = far_hops(insts, cols) > 1 or period > DEFAULT_MAX_PERIOD
+  lean = far_hops(insts, cols) > 1 or period > DEFAULT_MAX_PERIOD or mixed
   L = final.lag
-  vec_bytes = C * elem
+  vec_bytes = C * out_elem
   T_in = builtin_type(in_type)
   T_out = builtin_type(types[out_name])
 
@@ -416,7 +459,19 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=DEFAULT_
   emit_line('typedef %s %s __attribute__((ext_vector_type(%d), aligned(%d)));'
             % (T_in, vec_in, C, elem))
   emit_line('typedef %s %s __attribute__((ext_vector_type(%d), aligned(%d)));'
-            % (T_out, vec_out, C, elem))
+            % (T_out, vec_out, C, out_elem))
+  # every input is loaded through a vector of its OWN type, aligned to its own element: the
+  # first input's type shares `vec_in`, any other type gets one more
+  vec_piece = 'vec_%s_piece' % name
+  if vec_bytes > 16:
+    emit_line('typedef %s %s __attribute__((ext_vector_type(%d)));' % (
+        T_out, vec_piece, 16 // out_elem))
+  vec_of = {in_type: vec_in}
+  for t in spec['inputs']:
+    if t['c_type'] not in vec_of:
+      vec_of[t['c_type']] = '%s_%s' % (vec_in, t['name'])
+      emit_line('typedef %s %s __attribute__((ext_vector_type(%d), aligned(%d)));' % (
+          builtin_type(t['c_type']), vec_of[t['c_type']], C, specmod.ELEM_SIZE[t['c_type']]))
   emit_line('typedef unsigned soda_u2 __attribute__((ext_vector_type(2)));')
   emit_line('typedef unsigned soda_u4 __attribute__((ext_vector_type(4)));')
   if lean:
@@ -449,14 +504,16 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=DEFAULT_
   if steady:
     emit_line('  const bool st_full = x >= st_lo && x + %d <= st_hi;' % C)
   if flat:
-    emit_line('  const unsigned st_voff = st_full ? (unsigned)(x * %d) : 0xfffffff0u;' % elem)
+    # (pieces: the offsets of the later ones must not wrap past the sentinel)
+    emit_line('  const unsigned st_voff = st_full ? (unsigned)(x * %d) : 0x%xu;' % (
+        out_elem, 0xfffffff0 if vec_bytes <= 16 else 0x80000000))
   for inst in insts:
     # seam-free strips: a loaded row stays the VECTOR it arrived as until its cells are
     # used (sub-dword elements are unpacked there; unpacked at the load - behind the
     # scheduling fence of its step - every row would be waited for as soon as issued)
-    inst.packed = flat and inst.stage is None and inst.c_type == in_type
+    inst.packed = flat and inst.stage is None
     if inst.keep and inst.packed:
-      emit_line('  %s %s[%d];' % (vec_in, inst.ident, inst.keep))
+      emit_line('  %s %s[%d];' % (vec_of[inst.c_type], inst.ident, inst.keep))
     elif inst.keep:
       emit_line('  %s %s[%d][%d];' % (builtin_type(inst.c_type), inst.ident,
                                      inst.keep, C))
@@ -532,11 +589,12 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=DEFAULT_
           emit_line('        const %s* p = g_%s + row * W + x;' % (
               builtin_type(inst.c_type), inst.tensor))
           emit_line('        if (INTERIOR) {')
+          vec_row = vec_of[inst.c_type]
           if nontemporal & 1:
             emit_line('          const %s v = __builtin_nontemporal_load((const %s*)p);'
-                      % (vec_in, vec_in))
+                      % (vec_row, vec_row))
           else:
-            emit_line('          const %s v = *(const %s*)p;' % (vec_in, vec_in))
+            emit_line('          const %s v = *(const %s*)p;' % (vec_row, vec_row))
           if inst.packed:
             emit_line('          %s[%d] = v;' % (inst.ident, s))
           for c in range(0 if inst.packed else C):
@@ -603,16 +661,28 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=DEFAULT_
             # counts (behind a branch, and behind __builtin_nontemporal_store, it waits
             # for every access in flight: vmcnt(0) once per row or per trip)
             bits = {4: ('b32', 'unsigned'), 8: ('b64', 'soda_u2'),
-                    16: ('b128', 'soda_u4')}[vec_bytes]
+                    16: ('b128', 'soda_u4')}[min(vec_bytes, 16)]
+            aux = 'NT ? 2 : 0' if nt_auto else '2' if nontemporal & 2 else '0'
             emit_line('          if (!RAGGED) {')
-            emit_line('            %s v;' % vec_out)
-            for c in range(C):
-              emit_line('            v[%d] = out_row[%d];' % (c, c))
-            emit_line('            __builtin_amdgcn_raw_buffer_store_%s(__builtin_bit_cast(%s, v), '
-                      '__builtin_amdgcn_make_buffer_rsrc((void*)(g_out + y * W), 0, '
-                      '(int)(W * %d), 0x27000), st_voff, 0, %s);' % (
-                          bits[0], bits[1], elem, 'NT ? 2 : 0' if nt_auto else
-                          '2' if nontemporal & 2 else '0'))
+            if vec_bytes <= 16:
+              emit_line('            %s v;' % vec_out)
+              for c in range(C):
+                emit_line('            v[%d] = out_row[%d];' % (c, c))
+              emit_line('            __builtin_amdgcn_raw_buffer_store_%s(__builtin_bit_cast(%s, v), '
+                        '__builtin_amdgcn_make_buffer_rsrc((void*)(g_out + y * W), 0, '
+                        '(int)(W * %d), 0x27000), st_voff, 0, %s);' % (
+                            bits[0], bits[1], out_elem, aux))
+            else:
+              # the lane's row in 16-byte pieces, one store each, through one resource
+              per = 16 // out_elem
+              emit_line('            const auto rsrc = __builtin_amdgcn_make_buffer_rsrc('
+                        '(void*)(g_out + y * W), 0, (int)(W * %d), 0x27000);' % out_elem)
+              for piece in range(vec_bytes // 16):
+                emit_line('            { %s v; %s' % (vec_piece, ' '.join(
+                    'v[%d] = out_row[%d];' % (c, piece * per + c) for c in range(per))))
+                emit_line('              __builtin_amdgcn_raw_buffer_store_b128('
+                          '__builtin_bit_cast(soda_u4, v), rsrc, st_voff + %d, 0, %s); }' % (
+                              16 * piece, aux))
             emit_line('          } else if (%s >= st_lo && %s + %d <= st_hi) {' % (xq, xq, C))
           elif calm:
             emit_line('          if (RAGGED ? (%s >= st_lo && %s + %d <= st_hi) : st_full) {'
@@ -712,7 +782,7 @@ def emit(spec, depth, cols=None, chunk_rows=256, prefetch=3, max_period=DEFAULT_
     # (rows of 2 GiB or more: the branch-free store's buffer resource takes a signed
     # 32-bit size and 32-bit lane offsets; such rows keep the guarded path)
     emit_line('  const bool ragged = __builtin_amdgcn_ballot_w64(partial) != 0 || '
-              'a.dims[0] * %d >= 0x7ffffff0ll;' % elem)
+              'a.dims[0] * %d >= 0x7ffffff0ll;' % out_elem)
     emit_line('  if (!interior) %s_strip<false, true>(a, xs, x, y0, y1);' % name)
     emit_line('  else if (ragged) %s_strip<true, true>(a, xs, x, y0, y1);' % name)
     if nt_auto:

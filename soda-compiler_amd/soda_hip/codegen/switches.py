@@ -4,7 +4,8 @@ A switch is a boolean keyword of generate() that adds one kernel form to the pro
 class.  Everything outside the generator that has to know a switch - the command line, the
 generated hosts, the run-time's depth limit, the name of the prebuilt code object - reads it
 here: an opt-in form more is a row more - of SWITCHES, the forms for windows and outputs the
-default forms refuse, or of ELEMENT_SWITCHES, the forms by element width; readers take ALL.
+default forms refuse, or of ELEMENT_SWITCHES, the forms by element width, or of MIXED_SWITCHES, the forms for
+tensors of different widths; readers take EVERY.
 Data and pure functions only.  (The far-reach
 switches' depth limit depends on the program: depth_limit_of reads it off kernel.FAR_FORMS,
 where such a form is a row as well.)
@@ -62,7 +63,19 @@ ELEMENT_SWITCHES = (
            'run in the default schedule', '.pk', False, 'packed_cells'),
 )
 ALL = SWITCHES + ELEMENT_SWITCHES
-BY_KEYWORD = {s.keyword: s for s in ALL}
+# ... and the forms for programs whose tensors DIFFER in element width (ELEMENT_SWITCHES: one
+# narrow width throughout, cells packed; here: every tensor moved in its own width): a table of
+# their own with the same columns, a further such form is a row more here.  ALL stays the two
+# tables above; everything that reads the switches reads EVERY, the three tables in this order.
+MIXED_SWITCHES = (
+    Switch('mixed_widths', '--hip-mixed-widths', 'hip_mixed_widths',
+           'one fused depth-1 kernel for a 2-D program with one output whose inputs and '
+           'output differ in element width (8- or 16-bit pixels filtered in float, float '
+           'quantised to integers): every tensor is loaded and stored in its own width; it '
+           'runs in the default schedule', '.mw', False, 'mixed_widths'),
+)
+EVERY = ALL + MIXED_SWITCHES
+BY_KEYWORD = {s.keyword: s for s in EVERY}
 
 
 def given(on):
@@ -71,11 +84,11 @@ def given(on):
   for name in on:
     if name not in BY_KEYWORD:
       raise TypeError("got an unexpected keyword argument '%s'" % name)
-  return [s for s in ALL if on.get(s.keyword)]
+  return [s for s in EVERY if on.get(s.keyword)]
 
 
 def from_args(args, rows=SWITCHES):
-  """{keyword: bool} of every switch of `rows` (the command line reads ALL), read from an
+  """{keyword: bool} of every switch of `rows` (the command line reads EVERY), read from an
   argparse namespace."""
   return {s.keyword: bool(getattr(args, s.dest, False)) for s in rows}
 

@@ -512,8 +512,10 @@ def reference_init(spec, dims):
   for t in spec['inputs']:
     dt = np.dtype(specmod.NUMPY_NAME[t['c_type']])
     if floaty:
-      out.append(np.ascontiguousarray(
-          (s.astype(dt) / dt.type(sum(dims[:spec['dim']]))).astype(dt)))
+      # (an integer input next to a float first one: the reference's `T(p+q)/T(dims sum)`
+      # converts the divisor to T as C does, modulo 2^bits - uint8: 354 -> 98)
+      total = np.array(sum(dims[:spec['dim']]), dtype=np.int64).astype(dt)
+      out.append(np.ascontiguousarray((s.astype(dt) / total).astype(dt)))
     else:
       out.append(np.ascontiguousarray(s.astype(dt)))
   return out

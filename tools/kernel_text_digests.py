@@ -8,7 +8,8 @@ selection must give zero differing lines, the error lines included).
 The opt-in switches of generate() (fuse_outputs, lds_planes, lds_fields, lds_ring) are cases
 too (the cases of the first three are printed first and as they were before `lds_ring`
 existed, those with `lds_ring` after them, those with `far_lanes` after these, those with
-`far_taps` last: an older tree's output is a prefix-wise subset), and
+`far_taps` after those, those with `mixed_widths` last: an older tree's output is a
+prefix-wise subset), and
 what is derived from them outside the generator has lines of its own: `host/...`, the sha256
 of the generated Python and C++ host texts per combination of switches, and `file/...`, the
 name of the prebuilt code object per combination build() uses.
@@ -105,6 +106,7 @@ LDS_SAMPLES = [(app, dict(lds_planes=True)) for app in lds3d.APPS] + [
 RING_SAMPLES = [(app, dict(lds_ring=True)) for app in entry.LDS_RING_APPS]
 FAR_SAMPLES = [(app, dict(far_lanes=True)) for app in entry.FAR_LANES_APPS]
 TAPS_SAMPLES = [(app, dict(far_taps=True)) for app in entry.FAR_TAPS_APPS]
+MIXED_SAMPLES = [(app, dict(mixed_widths=True)) for app in entry.MIXED_WIDTHS_APPS]
 HOST_PROGRAMS = ('jacobi2d', 'grad2d', 'grad3d', 'star3d', 'acoustic3d', 'deriv3d')
 HOST_CPP_SWITCHES = ('fuse_outputs', 'lds_fields')      # the keywords host_cpp.print_code took
 
@@ -268,6 +270,18 @@ def cases():
     make = lambda t=text: specmod.spec_from_stencil(frontend.loads(t))
     for on in with_taps:
       yield 'inline/%s/%s' % (key, show(on)), make, on
+  # `mixed_widths`: alone on every sample and program text, and its samples in every lane
+  # shape of kernel.mixed_shapes (a shape over the register estimate keeps its stage kernels)
+  for path in sorted(glob.glob(os.path.join(SAMPLES, '*.soda')) +
+                     glob.glob(os.path.join(SAMPLES, 'extra', '*.soda'))):
+    app = os.path.basename(path)[:-5]
+    yield 'switch/%s/mixed_widths' % app, (lambda a=app: spec_of(a, None)), dict(mixed_widths=True)
+  for app, on in MIXED_SAMPLES:
+    for cols in sorted(kernel.mixed_shapes(spec_of(app, None))):
+      yield 'mixed_cols/%s/%d' % (app, cols), (lambda a=app: spec_of(a, None)), dict(on, cols=cols)
+  for key, text in inline_texts():
+    make = lambda t=text: specmod.spec_from_stencil(frontend.loads(t))
+    yield 'inline/%s/mixed_widths' % key, make, dict(mixed_widths=True)
 
 
 def digest(text):
@@ -317,6 +331,13 @@ def host_lines():
     yield 'host/shim/%s/far_taps %s' % (app, digest(out.getvalue()))
   for on in ({}, dict(far_taps=True)):
     for app in entry.FAR_TAPS_APPS:
+      yield 'file/%s/%s %s' % (app, show(on), os.path.basename(entry.blob_path(app, **on)))
+  for app in HOST_PROGRAMS + entry.MIXED_WIDTHS_APPS:
+    out = io.StringIO()
+    host_shim.print_code(spec_of(app, None), out, mixed_widths=True)
+    yield 'host/shim/%s/mixed_widths %s' % (app, digest(out.getvalue()))
+  for on in ({}, dict(mixed_widths=True)):
+    for app in entry.MIXED_WIDTHS_APPS:
       yield 'file/%s/%s %s' % (app, show(on), os.path.basename(entry.blob_path(app, **on)))
 
 
